@@ -28,6 +28,13 @@ Multi-GPU (torch.distributed over RCCL, one process per GPU):
   mc: every rank replays its share of the batch; no data-path collective
       ("scaling": "weak").
 
+A plain run stages the workload, warms up, times --steps steps and prints one
+JSON line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR also
+writes what the last timed step delivered (the consensus order and the
+per-call batch sizes) as DIR/<name>.npy: the inputs are seeded, so two builds
+can be compared output for output.  Everything below is measured or checked
+only with --full, after the timed steps, and added to the same line.
+
 The timed steps run without per-kernel instrumentation; a separate profiled
 pass (HIP events around every launch on the engine stream) gives every
 kernel's device time for the roofline.  Rank 0 also
@@ -172,6 +179,29 @@ def sub_stream(dag, ns):
     return {k: (v[:ns] if isinstance(v, np.ndarray) else v) for k, v in dag.items()}
 
 
+DUMP_BUDGET = 60 << 20  # bytes of --dump-outputs files (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` as path/<name>.npy, float32 where
+    that holds its integers exactly (below 2^24) and float64 otherwise.  The
+    smaller arrays are written whole; one that does not fit in its share of
+    DUMP_BUDGET is cut to a fixed sample (sorted indices drawn with seed 0, the
+    same for every run of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET
+    items = sorted(arrays.items(), key=lambda kv: np.size(kv[1]))
+    for i, (name, a) in enumerate(items):
+        a = np.asarray(a).ravel()
+        exact32 = a.size == 0 or int(np.abs(a).max()) < 1 << 24
+        a = a.astype(np.float32 if exact32 else np.float64)
+        cap = left // (len(items) - i) // a.itemsize
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def online_path(n, E, K, seed, device, dag=None, what=None):
     """The per-call production path: for every call, hge_insert_events of the
     next K submissions, then hge_run_consensus (node/core.go:179-202).  Returns
@@ -308,9 +338,10 @@ def mc_main(args, n, E, K, rank, world, local_rank, dist):
 
 def mc_line(args, n, E, K, rank, world, local_rank, dist, cpu_s=10.0):
     """Config 5 on the batch engine: this rank's share of the Monte Carlo batch,
-    one replay of all of it per step (five launches), every graph checked
-    against the oracle's committed full-state digest.  Returns rank 0's line
-    (None elsewhere); the CPU baseline takes about `cpu_s` seconds."""
+    one replay of all of it per step (five launches).  Returns rank 0's line
+    (None elsewhere).  With --full (mc_full) every graph is checked against the
+    oracle's committed full-state digest and the CPU baseline takes about
+    `cpu_s` seconds."""
     from babble_amd.dist import reduce_step, shard_range
     from babble_amd.engine import Batch
     from babble_amd.gossip import random_gossip, schedule
@@ -344,16 +375,64 @@ def mc_line(args, n, E, K, rank, world, local_rank, dist, cpu_s=10.0):
     ordered = 0
     for _ in range(args.steps):
         ordered = batch.run()
-        for k_, v_ in batch.kernel_ms().items():  # HIP events between the launches, on the batch stream
-            kacc[k_] = kacc.get(k_, 0.0) + v_
+        if args.full:
+            for k_, v_ in batch.kernel_ms().items():  # HIP events between the launches, on the batch stream
+                kacc[k_] = kacc.get(k_, 0.0) + v_
     t1 = time.perf_counter()
     sync_all()
     step_s = (t1 - t0) / args.steps
-    kms = {k_: v_ / args.steps for k_, v_ in kacc.items()}
     tot_ordered, max_step = ordered, step_s
     if dist is not None:
         max_step, tot_ordered = reduce_step(dist, step_s, ordered, f"cuda:{local_rank}")
 
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step left for a caller: every graph's order and per-call
+        # batch sizes, in graph order (this rank's share of the batch)
+        states = [batch.state(g) for g in range(per)]
+        dump_outputs(args.dump_outputs, {"order": np.concatenate([s["order"] for s in states]),
+                                         "counts": np.concatenate([s["counts"] for s in states]),
+                                         "n_ordered": np.array([ordered])})
+        del states
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "consensus-ordered events/sec at N participants",
+            "value": round(tot_ordered / max_step, 1),
+            "unit": "events/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(max_step * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int32",
+            "data": "synthetic",
+            "config": {"workload": (f"Monte Carlo batch: {args.graphs} independent random-gossip hashgraphs, "
+                                    f"{n} participants, {E} submissions each, 10 forkers p=0.05 with cascades, "
+                                    f"RunConsensus every K={K}"),
+                       "participants": n, "events_per_graph": E, "k": K, "graphs_per_gpu": per,
+                       "ordered_per_step": tot_ordered,
+                       "parallelism": f"replicas{world}: the batch split across {world} GPUs, no collective"},
+            "ingest_host_ms": round(ingest_s * 1e3, 2),
+            "admission_ms": round(admission_s * 1e3, 2),
+        }
+    if args.full:
+        full = mc_full(args, n, E, K, rank, world, local_rank, dist, batch, dags, first, per, events, ordered,
+                       tot_ordered / max_step, {k_: v_ / args.steps for k_, v_ in kacc.items()}, cpu_s)
+        if line is not None:
+            line.update(full)
+    batch.close()
+    return line
+
+
+def mc_full(args, n, E, K, rank, world, local_rank, dist, batch, dags, first, per, events, ordered, value, kms,
+            cpu_s):
+    """--full for the batch engine: every graph of this rank against the oracle's
+    committed digests, the CPU baseline, and the per-kernel roofline figures.
+    Every rank takes part (the digest counts are all-reduced); the returned
+    fields are rank 0's."""
+    from babble_amd.gossip import schedule
     rounds_tot = sum(batch.info(g)["rounds"] for g in range(per))
     calls_tot = sum(batch.info(g)["calls"] for g in range(per))
     # every graph of this rank against the oracle's full-state digest
@@ -397,34 +476,14 @@ def mc_line(args, n, E, K, rank, world, local_rank, dist, cpu_s=10.0):
                          f"of the batch (whole graphs, K={K}), {tot} ordered in {cs:.2f} s on "
                          f"{platform.processor() or platform.machine()} (host nproc {os.cpu_count()})"}
     if rank != 0:
-        batch.close()
-        return None
-    value = tot_ordered / max_step
+        return {}
     dom = max(kms, key=kms.get)
     kb = {k_: mc_kernel_bytes(k_, n, events, ordered, rounds_tot, calls_tot) for k_ in kms}
     alg = kb[dom]
     achieved = alg / (kms[dom] * 1e-3) / 1e9
     hbm = {k_: {"ms": round(v_, 4), "alg_bytes": kb[k_], "achieved_gbs": round(kb[k_] / (v_ * 1e-3) / 1e9, 2)}
            for k_, v_ in kms.items()}
-    line = {
-        "metric": "consensus-ordered events/sec at N participants",
-        "value": round(value, 1),
-        "unit": "events/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(max_step * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int32",
-        "data": "synthetic",
-        "config": {"workload": (f"Monte Carlo batch: {args.graphs} independent random-gossip hashgraphs, "
-                                f"{n} participants, {E} submissions each, 10 forkers p=0.05 with cascades, "
-                                f"RunConsensus every K={K}"),
-                   "participants": n, "events_per_graph": E, "k": K, "graphs_per_gpu": per,
-                   "ordered_per_step": tot_ordered,
-                   "parallelism": f"replicas{world}: the batch split across {world} GPUs, no collective"},
+    return {
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
                      "traffic": pmc_traffic(f"mc_n{n}_e{E}_k{K}_g{args.graphs}" if world == 1 else None, dom, 1),
@@ -435,15 +494,11 @@ def mc_line(args, n, E, K, rank, world, local_rank, dist, cpu_s=10.0):
                               "frac": round(value / world * (24 * n + 48) / 1e9 / HBM_PEAK_GBS, 5)}},
         "cpu_baseline": cpu,
         "parity": "; ".join(checks) if checks else None,
-        "ingest_host_ms": round(ingest_s * 1e3, 2),
-        "admission_ms": round(admission_s * 1e3, 2),
         "kernels_ms_per_replay": {k_: round(v_, 4) for k_, v_ in sorted(kms.items(), key=lambda kv: -kv[1])},
         "kernel_launches_per_replay": {"kb_coords": 1 if per > 512 else 2, "kb_fd": 1, "kb_fdrows": 1, "kb_front": 1, "kb_fame": 2,
                                        "kb_fold": 2, "kb_receive": 1, "kb_order": 2},
         "graphs_replayed_call_by_call": batch.fallbacks(),
     }
-    batch.close()
-    return line
 
 
 def main():
@@ -459,11 +514,16 @@ def main():
     ap.add_argument("--k", type=int, default=None, help="RunConsensus every k submissions")
     ap.add_argument("--graphs", type=int, default=1024, help="mc: hashgraphs in the whole batch")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (order, per-call counts) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled pass and roofline, the parity checks, "
+                         "the CPU baseline and the secondary workloads (the options below narrow it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary workloads")
     ap.add_argument("--cpu-sample-events", type=int, default=None,
-                    help="CPU baseline prefix (default: 20480 at N >= 128, 100k below)")
-    ap.add_argument("--profile-steps", type=int, default=1)
+                    help="--full: CPU baseline prefix (default: 20480 at N >= 128, 100k below)")
+    ap.add_argument("--profile-steps", type=int, default=1, help="--full: replays of the profiled pass")
     ap.add_argument("--replicas", action="store_true",
                     help="gossip, N > 1: one independent hashgraph per rank (weak scaling) instead of "
                          "ONE hashgraph sharded across the ranks (babble_amd.dist.split_run)")
@@ -543,10 +603,69 @@ def main():
     t1 = time.perf_counter()
     sync_all()
     step_s = (t1 - t0) / args.steps
+    eng0 = engines[0]
+
+    def headline(tot_ordered, max_step):
+        workload = (f"random-gossip DAG, {n} participants, {E} events "
+                    f"{'in one hashgraph' if split else 'per GPU'}, "
+                    f"RunConsensus every K={K} events ({len(schedule(E, K))} calls)")
+        return {
+            "metric": "consensus-ordered events/sec at N participants",
+            "value": round(tot_ordered / max_step, 1),
+            "unit": "events/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(max_step * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "strong" if split else "weak",
+            "vs_baseline": None,
+            "dtype": "int32",
+            "data": "synthetic",
+            "config": {"workload": workload, "participants": n, "events_per_graph": E, "k": K,
+                       "graphs_per_gpu": 1, "ordered_per_step": tot_ordered,
+                       "parallelism": ((f"shard{world}: one hashgraph sharded by time across {world} GPUs "
+                                        f"(fame by round, round received / median / order by call; RCCL "
+                                        f"all-gathers; coordinates and the sequential rounds walk on every "
+                                        f"rank)") if split else f"replicas{world}")},
+            "ingest_host_ms": round(ingest_s * 1e3, 2),
+            "admission_ms": None if admission_s is None else round(admission_s * 1e3, 2),
+        }
+
+    def finish():
+        for e in engines:
+            e.close()
+        if os.environ.get("HGE_DUMP_MAPS"):
+            # diagnostics for crashes after main (rocprofv3 exit SIGSEGV): the library map
+            with open("/proc/self/maps") as f, open(os.environ["HGE_DUMP_MAPS"], "w") as g:
+                g.write(f.read())
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step delivered: the consensus order and the per-call batch sizes
+        _, dorder, dcounts = eng0.fetch()
+        dump_outputs(args.dump_outputs, {"order": dorder, "counts": dcounts, "n_ordered": np.array([ordered])})
+        del dorder, dcounts
+    tot_ordered, max_step = ordered, step_s
+    if dist is not None:
+        max_step, tot_ordered = reduce_step(dist, step_s, ordered, f"cuda:{local_rank}")
+        if split:
+            tot_ordered = ordered  # one hashgraph for the whole job
+    line = None
+    if rank == 0:
+        line = headline(tot_ordered, max_step)
+        if split:
+            # timed steps that fell back to the unsplit replay (HGE_ERR_SPLIT): 0 means
+            # every timed step ran sharded
+            line["split_fallbacks"] = split_stats.get("fallback", 0) - f0
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        finish()
+        return
 
     # ---- one more unprofiled replay: GPU-busy vs wall split of a step ----
-    eng0 = engines[0]
-    nfall = split_stats.get("fallback", 0) - f0
     if split:
         sync_all()
         step()
@@ -574,12 +693,6 @@ def main():
     ev0 = len(dags[0]["creator"])
     ord0 = eng0._nordered
     sweeps = eng0.coordinate_sweeps()
-
-    tot_ordered, max_step = ordered, step_s
-    if dist is not None:
-        max_step, tot_ordered = reduce_step(dist, step_s, ordered, f"cuda:{local_rank}")
-        if split:
-            tot_ordered = ordered  # one hashgraph for the whole job
 
     def kernel_roofline(name):
         """(algorithmic bytes per launch, average launch ms, achieved GB/s).
@@ -696,33 +809,13 @@ def main():
         import copy
         mca = copy.copy(args)
         mca.graphs = 1024
+        mca.dump_outputs = None  # the dump is the headline workload's
         secondary["mc_1024x32x10k"] = mc_line(mca, 32, 10_000, 32, 0, 1, local_rank, None, cpu_s=5.0)
 
     if rank == 0:
         value = tot_ordered / max_step
-        workload = (f"random-gossip DAG, {n} participants, {E} events "
-                    f"{'in one hashgraph' if split else 'per GPU'}, "
-                    f"RunConsensus every K={K} events ({len(schedule(E, K))} calls)")
         cfg_key = f"{args.workload}_n{n}_e{E}_k{K}"
-        line = {
-            "metric": "consensus-ordered events/sec at N participants",
-            "value": round(value, 1),
-            "unit": "events/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(max_step * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if split else "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic",
-            "config": {"workload": workload, "participants": n, "events_per_graph": E, "k": K,
-                       "graphs_per_gpu": 1, "ordered_per_step": tot_ordered,
-                       "parallelism": ((f"shard{world}: one hashgraph sharded by time across {world} GPUs "
-                                        f"(fame by round, round received / median / order by call; RCCL "
-                                        f"all-gathers; coordinates and the sequential rounds walk on every "
-                                        f"rank)") if split else f"replicas{world}")},
+        line.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 5),
@@ -737,8 +830,6 @@ def main():
                                   "frac": round(value / world * (24 * n + 48) / 1e9 / HBM_PEAK_GBS, 5)}},
             "cpu_baseline": cpu,
             "parity": parity,
-            "ingest_host_ms": round(ingest_s * 1e3, 2),
-            "admission_ms": None if admission_s is None else round(admission_s * 1e3, 2),
             "replay_ms": replay_ms,
             "order_fetch_copy_ms": round(order_fetch_ms, 3),
             "coordinate_sweeps": sweeps,
@@ -746,22 +837,11 @@ def main():
             "kernels_ms_per_replay": {k: round(v[0] / nprof, 4) for k, v in
                                       sorted(kstats.items(), key=lambda kv: -kv[1][0])},
             "kernel_launches_per_replay": {k: v[1] // nprof for k, v in kstats.items()},
-        }
-        if split:
-            # timed steps that fell back to the unsplit replay (HGE_ERR_SPLIT): 0 means
-            # every timed step ran sharded
-            line["split_fallbacks"] = nfall
+        })
         if secondary is not None:
             line["secondary"] = secondary
         print(json.dumps(line), flush=True)
-    for e in engines:
-        e.close()
-    if os.environ.get("HGE_DUMP_MAPS"):
-        # diagnostics for crashes after main (rocprofv3 exit SIGSEGV): the library map
-        with open("/proc/self/maps") as f, open(os.environ["HGE_DUMP_MAPS"], "w") as g:
-            g.write(f.read())
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@ OUT=gpurun_out/${1:-calib}
 mkdir -p $OUT
 timeout -k 10 200 python -u scripts/fetch_calib.py $OUT > $OUT/calib.log 2>&1 || { tail -30 $OUT/calib.log; exit 1; }
 tail -1 $OUT/calib.log
-timeout -k 10 500 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 2; }
+timeout -k 10 500 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 2; }
 python -c "
 import json
 d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ shift
 ARGS=${*:---graphs 1024}
 mkdir -p $OUT
 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_INSTS_SALU --output-format csv -d $OUT/sq -o pmc -- \
-  python3 bench.py --workload mc --no-cpu-baseline --steps 1 --warmup 0 --ramp-s 0 $ARGS > $OUT/sq.log 2>&1 || { echo "sq pass failed"; tail -5 $OUT/sq.log; exit 1; }
+  python3 bench.py --workload mc --full --no-cpu-baseline --steps 1 --warmup 0 --ramp-s 0 $ARGS > $OUT/sq.log 2>&1 || { echo "sq pass failed"; tail -5 $OUT/sq.log; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, glob, os, sys
 per = {}

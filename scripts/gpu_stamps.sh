@@ -4,7 +4,7 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-stamps}
 mkdir -p $OUT
-HGE_LIB=build/libhge_stamps.so HGE_STAMPS=1 timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-secondary --participants 256 --events ${STAMP_EVENTS:-2000000} --steps 1 --warmup 0 --ramp-s 0 --profile-steps 1 > $OUT/st.json 2> $OUT/st.err || { tail -20 $OUT/st.err; exit 1; }
+HGE_LIB=build/libhge_stamps.so HGE_STAMPS=1 timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-secondary --participants 256 --events ${STAMP_EVENTS:-2000000} --steps 1 --warmup 0 --ramp-s 0 --profile-steps 1 > $OUT/st.json 2> $OUT/st.err || { tail -20 $OUT/st.err; exit 1; }
 grep "hge stamps" $OUT/st.err | tail -3
 python -c "
 import json

@@ -28,7 +28,7 @@ def main():
     if not parse_only:
         cmd = ["timeout", "-s", "KILL", "240", "rocprofv3", "--kernel-trace", "--pmc"] + counters + [
             "--output-format", "csv", "-d", d, "-o", "pmc", "--", "python3", "bench.py",
-            "--no-cpu-baseline", "--profile-steps", "1", "--ramp-s", "0"] + bench_args
+            "--full", "--no-cpu-baseline", "--profile-steps", "1", "--ramp-s", "0"] + bench_args
         subprocess.check_call(cmd, cwd=ROOT)
     per = {}
     for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):

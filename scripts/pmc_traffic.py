@@ -26,7 +26,7 @@ def run_pass(out_dir, counter, bench_args, parse_only=False):
     if not parse_only:
         cmd = ["timeout", "-s", "KILL", "240", "rocprofv3", "--kernel-trace", "--pmc", counter,
                "--output-format", "csv", "-d", d, "-o", "pmc", "--", "python3", "bench.py",
-               "--no-cpu-baseline", "--no-secondary", "--profile-steps", "1"] + bench_args
+               "--full", "--no-cpu-baseline", "--no-secondary", "--profile-steps", "1"] + bench_args
         subprocess.check_call(cmd, cwd=ROOT)
     files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
     if not files:
