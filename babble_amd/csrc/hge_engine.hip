@@ -18,11 +18,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/hge.h"
+#include "hge_plan.h"
 #include "hge_kernels.hip"
 #include "hge_wide32.hip"
 #include "hge_coords.hip"
@@ -53,6 +55,34 @@ using namespace hge;
       throw EngineError(HGE_ERR_DEVICE, std::string("launch " #kern ": ") + hipGetErrorString(le_)); \
     prof_end();                                                                        \
   } while (0)
+
+// Run-time NW (1..4) -> template argument, the one place that does it:
+//   KLAUNCH_NW(NW, SHAPE, kernel, [template arguments around the width,] launch arguments...)
+// SHAPE says where the width goes and whether the name is parenthesised, so that each
+// case hands KLAUNCH the kernel with the number in place and hge_kernel_stats keeps
+// reporting "k_median_wave<4>" and "(k_fame_call<64, 4, false>)" (bench.py reads them).
+// KLAUNCH_NW2: N > 64 only (no <1> instance of the kernel exists).
+#define NW_T(B, kern, ...) KLAUNCH(kern<B>, __VA_ARGS__)
+#define NW_PT(B, kern, ...) KLAUNCH((kern<B>), __VA_ARGS__)
+#define NW_PAT(B, kern, A, ...) KLAUNCH((kern<A, B>), __VA_ARGS__)
+#define NW_PATC(B, kern, A, C, ...) KLAUNCH((kern<A, B, C>), __VA_ARGS__)
+#define NW_SWITCH_(nw, CASE1, SHAPE, ...)                          \
+  switch (nw) {                                                    \
+    CASE1                                                          \
+    case 2:                                                        \
+      SHAPE(2, __VA_ARGS__);                                       \
+      break;                                                       \
+    case 3:                                                        \
+      SHAPE(3, __VA_ARGS__);                                       \
+      break;                                                       \
+    case 4:                                                        \
+      SHAPE(4, __VA_ARGS__);                                       \
+      break;                                                       \
+    default:                                                       \
+      throw EngineError(HGE_ERR_INTERNAL, "unsupported N");        \
+  }
+#define KLAUNCH_NW(nw, SHAPE, ...) NW_SWITCH_(nw, case 1 : SHAPE(1, __VA_ARGS__); break;, SHAPE, __VA_ARGS__)
+#define KLAUNCH_NW2(nw, SHAPE, ...) NW_SWITCH_(nw, , SHAPE, __VA_ARGS__)
 
 namespace {
 
@@ -127,12 +157,15 @@ struct hge_engine {
   // N > 32 past chain_limit: int32 positions for good (hge_wide32.hip); pending until
   // the next coordinate step converts the packed table
   bool wide32 = false, wide32_pending = false;
+  // to_wide32's progress bits: 1 the runs widened, 2 the FD rows, 4 the int32 LA table allocated
   int w32_done = 0;
-  // an internal failure that left the host and device state apart: every later
-  // consensus call refuses (HGE_ERR_INTERNAL) until a new stream (hge_replay_prepare)
-  std::string failed;  // to_wide32's progress: 1 the runs widened, 2 the FD rows, 4 the int32 LA table allocated
-  // test hook (HGE_TEST_W32_FAIL=k): to_wide32 fails once after its stage k (1 the int32
-  // LA table allocated, 2 the runs widened, 3 the FD rows widened)
+  // what failed, when an internal failure left the host and device state apart (empty:
+  // none): every later consensus call refuses (HGE_ERR_INTERNAL) until a new stream
+  // (hge_replay_prepare)
+  std::string failed;
+  // test hook (HGE_TEST_W32_FAIL=k): to_wide32 fails once after its stage k.  Stages count
+  // in the order to_wide32 runs them, not by bit value: 1 the int32 LA table allocated
+  // (bit 4), 2 the runs widened (bit 1), 3 the FD rows widened (bit 2)
   int test_w32_fail = getenv("HGE_TEST_W32_FAIL") ? atoi(getenv("HGE_TEST_W32_FAIL")) : 0;
   int lcr = -1;             // LastConsensusRound (-1 nil)
   int lcre = 0;             // LastCommitedRoundEvents
@@ -1068,6 +1101,26 @@ struct hge_engine {
     cs_tot0 = tot0;
     return true;
   }
+  // what a single-block rounds walk does after walking: the rounds of the new events
+  // [n0, n1) (k_round_assign's work; und_appended: their ids appended to the
+  // undetermined list) and, with `tail`, k_round_tail's work
+  RoundAssign round_assign(int64_t n0, int64_t n1, bool tail) {
+    s_newwit.need(n1 - n0);
+    RoundAssign ra{(int)n0, (int)n1, s_newwit.p, k_rs + 2, und_appended ? d_und.p + n_und : (int32_t*)nullptr};
+    if (tail) {
+      int Gw = 1;
+      while (Gw < std::min(N, 64)) Gw <<= 1;
+      ra.minw = d_minw.p;
+      ra.G = Gw;
+      ra.und = d_und.p;
+      ra.n_und = (int)n_und;
+      ra.lo = (int)n_divided;
+      ra.hi = (int)n1;
+      ra.r_from = minw_full ? 0 : -1;
+      ra.rlo_dev = s_fst.p;
+    }
+    return ra;
+  }
   void coords_b() {
     cs_pending = false;
     const bool fresh = cs_fresh;
@@ -1108,25 +1161,11 @@ struct hge_engine {
           const int64_t guess = m + 16 * (int64_t)N;  // the grid loops past it
           // the walk's block also assigns the new events' rounds (k_round_assign's work)
           und_appended = dividing && n_divided == n0;
-          s_newwit.need(m);
-          RoundAssign ra{(int)n0, (int)n1, s_newwit.p, k_rs + 2,
-                         und_appended ? d_und.p + n_und : (int32_t*)nullptr};
-          asg_fused = true;
           // ... and k_round_tail's work (the new witnesses' bitsets, the first witness
           // of the rounds from the walk's first one, the candidates' lowest round)
-          if (n_und + (n1 - n_divided) <= 65536) {
-            int Gw = 1;
-            while (Gw < std::min(N, 64)) Gw <<= 1;
-            ra.minw = d_minw.p;
-            ra.G = Gw;
-            ra.und = d_und.p;
-            ra.n_und = (int)n_und;
-            ra.lo = (int)n_divided;
-            ra.hi = (int)n1;
-            ra.r_from = minw_full ? 0 : -1;
-            ra.rlo_dev = s_fst.p;
-            tail_fused = true;
-          }
+          tail_fused = n_und + (n1 - n_divided) <= 65536;
+          const RoundAssign ra = round_assign(n0, n1, tail_fused);
+          asg_fused = true;
 #define FSSD(NPC, LPC, B)                                                                              \
   KLAUNCH(k_fss<NPC>, dim3((unsigned)std::min<int64_t>(1024, div_up(guess * NPC, 256))), dim3(256), 0, st, t, \
           k_lo, k_lo + N, 0, (int32_t*)nullptr, (uint16_t*)d_FSS.p, (const int32_t*)(k_lo + 2 * N));          \
@@ -1885,198 +1924,229 @@ struct hge_engine {
   // calls: event counts n_c (<= n_divided), ascending.
   // Host round trips: the fame-window coverage flags, the lowest candidate round
   // of an online batch, the segment count for N > 64, and one closing readback.
-  // Control data goes up as one block (s_cctl), results come back as one block
-  // (s_out: counters, per-call counts, order).
-  void consensus_batch(const std::vector<int64_t>& calls, bool do_fame, bool do_order,
-                       bool commit, std::vector<int32_t>* order_out,
-                       std::vector<int64_t>* counts_out) {
-    const int ncalls = (int)calls.size();
-    if (ncalls == 0) return;
-    const bool tph = ncalls > 1000 && getenv("HGE_HOST_PHASES");
-    int64_t tp[6] = {now_ns(), 0, 0, 0, 0, 0};
-    consensus_sync();  // (the results block is reused below)
-    Tables t = tables();
-    x_iter = 0;
-    // R_c = Rounds() after the DivideRounds of call c = #{r : minw[r] < n_c}
-    // (one merge pass over the ascending calls and first witnesses: 39k binary searches
-    // were ~0.5 ms of idle GPU at the start of a 256/10M replay's consensus)
-    std::vector<int32_t> Rc(ncalls);
-    for (int c = 0, r = 0; c < ncalls; c++) {
-      if (c > 0 && calls[c] < calls[c - 1])  // (not ascending: search afresh)
-        r = (int)(std::lower_bound(h_minw.begin(), h_minw.end(), calls[c],
-                                   [](int32_t m, int64_t n) { return (int64_t)m < n; }) -
-                  h_minw.begin());
-      while (r < (int)h_minw.size() && (int64_t)h_minw[r] < calls[c]) r++;
-      Rc[c] = r;
+  // Control data goes up as one block (s_cctl, hge_plan::CtlLayout), results come back
+  // as one block (s_out, hge_plan::ResultsLayout: counters, per-call counts, order).
+
+  // how the order's stages were launched
+  enum class OrderRan {
+    Stages,     // every stage as its own grid
+    CallFront,  // all of them in one block (k_order_call front = 1, or k_consensus_call)
+    CallTail,   // the stage grids up to round received, then k_order_call front = 0
+  };
+  // what one batch's stages share
+  struct Batch {
+    const int64_t* calls = nullptr;
+    int ncalls = 0;
+    bool do_fame = false, do_order = false, commit = false;
+    std::vector<int32_t>* order_out = nullptr;
+    std::vector<int64_t>* counts_out = nullptr;
+    // ---- the prologue's
+    std::vector<int32_t> Rc;   // Rounds() at each call
+    bool fresh_und = false;    // the candidates are every event of a fresh replay
+    bool ord = false;          // there are candidates to order
+    bool spl = false;          // a split part: the candidates of its own range
+    int32_t* cand = nullptr;
+    int ncand = 0;
+    int rr_lo = 0, R_last = 0, nr = 0;  // the order pass examines rounds [rr_lo, rr_lo + nr)
+    hge_plan::ResultsLayout out;
+    // ---- decide_fame's
+    hge_plan::FameWindows w;
+    hge_plan::CtlLayout ctl;
+    int64_t nslot = 0;
+    bool hdr_done = false;  // the fame launch wrote the results header
+    // every round's window reaches the last call (always so for one call: the online
+    // path), so none can widen: the coverage flags stay on the device, and the new
+    // LastConsensusRound comes back with the batch's closing readback
+    bool lcr_dev = false;
+    int lcr_new = -1, c_set = -1;  // !lcr_dev: the new LastConsensusRound and the call that set it
+    bool lcr_up = false;
+    // N <= 16: k_fame_call waits to run with the order (k_consensus_call)
+    std::optional<FameCall> fame_pending;
+    // ---- the order's
+    SegInfo si{};
+    OrderRan order_ran = OrderRan::Stages;
+    bool wla_done = false;
+    bool got_order = false;
+    bool wrote_direct = false;  // the bucket sorts wrote the ids into the pinned order buffer
+    bool split_done = false;
+  };
+  int32_t* out_counts() const { return s_out.p + hge_plan::ResultsLayout::kCounts; }
+  int32_t* out_ids(const Batch& b) const { return s_out.p + b.out.ids; }
+  unsigned long long* out_tx(const Batch& b) const { return (unsigned long long*)(s_out.p + b.out.o_tx); }
+  int32_t* out_word(size_t k) const { return s_out.p + k; }
+  // the new LastConsensusRound for the results header, when the device holds it
+  const int32_t* lcr_src(const Batch& b) const { return b.lcr_dev ? (const int32_t*)(c_flags + 1) : nullptr; }
+  void out_init(const Batch& b) {
+    const int nh = (int)b.out.header();
+    KLAUNCH(k_out_init, dim3(div_up(nh, 256)), dim3(256), 0, st, s_out.p, nh, lcr_src(b));
+  }
+  // the control block's regions in s_cctl (host-built, or k_consensus_dyn's to fill)
+  void bind_ctl(const hge_plan::CtlLayout& L) {
+    c_nc = (int64_t*)s_cctl.p;
+    c_Rc = s_cctl.p + L.Rc;
+    c_Lc = s_cctl.p + L.Lc;
+    c_flags = s_cctl.p + L.flags;
+    c_pr = s_cctl.p + L.pr;
+    c_pidx = s_cctl.p + L.pidx;
+    c_sgo = s_cctl.p + L.sgo;
+  }
+
+  void consensus_batch(const std::vector<int64_t>& calls, bool do_fame, bool do_order, bool commit,
+                       std::vector<int32_t>* order_out, std::vector<int64_t>* counts_out) {
+    if (calls.empty()) return;
+    int64_t tp[5] = {now_ns(), 0, 0, 0, 0};
+    Batch b;
+    b.calls = calls.data();
+    b.ncalls = (int)calls.size();
+    b.do_fame = do_fame;
+    b.do_order = do_order;
+    b.commit = commit;
+    b.order_out = order_out;
+    b.counts_out = counts_out;
+    prologue(b, calls);
+    tp[1] = now_ns();
+    decide_fame(b);
+    tp[2] = now_ns();
+    if (b.ord) {
+      order_stages(b);
+      bucket_and_sort(b);
+    } else {  // nothing to order: the results header alone
+      s_out.need(b.out.total());
+      launch_pending_fame(b);
+      if (!b.hdr_done) out_init(b);
     }
-    const bool fresh_und = und_fresh;
+    if (b.fame_pending) throw EngineError(HGE_ERR_INTERNAL, "DecideFame's launch left pending");
+    persist_fame(b);
+    if (b.spl && b.got_order) {  // the parts' ordered slices, joined in call order
+      split_commit(s_out.p, out_counts(), out_ids(b), b.out.ntxb, out_tx(b), order_out, counts_out);
+      b.got_order = false;
+      b.split_done = true;
+    }
+    tp[3] = now_ns();
+    close_batch(b);
+    tp[4] = now_ns();
+    if (b.ncalls > 1000 && getenv("HGE_HOST_PHASES")) phases_line(tp);
+    prof_collect();
+  }
+  void phases_line(const int64_t* tp) const {
+    fprintf(stderr, "[hge consensus] prologue %.3f ms, fame %.3f ms (incl. syncs), order enqueue %.3f ms, closing %.3f ms\n",
+            (tp[1] - tp[0]) / 1e6, (tp[2] - tp[1]) / 1e6, (tp[3] - tp[2]) / 1e6, (tp[4] - tp[3]) / 1e6);
+  }
+
+  // R_c, the candidates and their lowest round, the order pass's rounds, the results layout
+  void prologue(Batch& b, const std::vector<int64_t>& calls) {
+    consensus_sync();  // (the results block is reused below)
+    x_iter = 0;
+    b.Rc = hge_plan::rounds_at_calls(calls, h_minw);
+    b.fresh_und = und_fresh;
     und_fresh = false;
-    const bool ord = do_order && n_und > 0;
-    int ncand = (int)n_und;
-    int32_t* cand = d_und.p;
+    b.ord = b.do_order && n_und > 0;
+    b.ncand = (int)n_und;
+    b.cand = d_und.p;
     // a split part's candidates: the events [cand_lo, its end) of the fresh list (identity)
-    const bool spl = split_on() && ord && fresh_und;
-    if (spl) {
-      cand = d_und.p + sp.clo[sp.part];
-      ncand = (int)(sp.a[sp.part + 1] - sp.clo[sp.part]);
+    b.spl = split_on() && b.ord && b.fresh_und;
+    if (b.spl) {
+      b.cand = d_und.p + sp.clo[sp.part];
+      b.ncand = (int)(sp.a[sp.part + 1] - sp.clo[sp.part]);
     }
     // lowest candidate round (a fresh replay's candidates include event 0, round 0)
     int32_t mnr = 0;
-    const bool pre = mnr_key[0] >= 0 && !spl && n_divided == mnr_key[2] &&
+    const bool pre = mnr_key[0] >= 0 && !b.spl && n_divided == mnr_key[2] &&
                      n_und == mnr_key[0] + (mnr_key[2] - mnr_key[1]);
     mnr_key[0] = -1;
-    if (ord && !fresh_und && pre) {
+    if (b.ord && !b.fresh_und && pre) {
       mnr = mnr_pre;
-    } else if (ord && (!fresh_und || spl)) {
+    } else if (b.ord && (!b.fresh_und || b.spl)) {
       h2d(s_small.p + 7, &kInf, 4);
-      KLAUNCH(k_min_round, dim3(div_up(ncand, 256)), dim3(256), 0, st, d_round.p, cand, ncand,
+      KLAUNCH(k_min_round, dim3(div_up(b.ncand, 256)), dim3(256), 0, st, d_round.p, b.cand, b.ncand,
               s_small.p + 7);
       readback(&mnr, s_small.p + 7, 1);
     }
-    const int rr_lo = mnr + 1;
+    b.rr_lo = mnr + 1;
     // a split part's calls end at its last one: later rounds receive nothing it commits
-    const int R_last = spl ? Rc[sp.cb[sp.part + 1] - 1] : Rc[ncalls - 1];
-    const int nr = ord ? std::max(0, R_last - rr_lo) : 0;
+    b.R_last = b.spl ? b.Rc[sp.cb[sp.part + 1] - 1] : b.Rc[b.ncalls - 1];
+    b.nr = b.ord ? std::max(0, b.R_last - b.rr_lo) : 0;
+    // the results block's size is known before DecideFame: the single-call fame kernel
+    // writes its header
+    b.out = hge_plan::results_layout(b.ncalls, b.ord ? b.ncand : 0);
+  }
 
-    // the results block's size (counters | per-call counts | order | per-block transaction
-    // sums), known before DecideFame: the single-call fame kernel writes its header
-    const size_t o_tx0 = (8 + (size_t)ncalls + (ord ? ncand : 0) + 1) & ~(size_t)1;
-    const int ntxb0 = ord ? div_up(ncand, 256) : 0;
-    bool hdr_done = false;
-    bool ocall = false;  // the order's stages ran as one launch (k_order_call)
-    bool fame_deferred = false;  // N <= 16: k_fame_call waits to run with the order (k_consensus_call)
-    FameCall fc_pend{};
-    auto fame_call_args = [&](int nrounds_, int npairs_, int ncalls_, int32_t* hdr) {
-      FameCall f{};
-      f.pr_round = c_pr;
-      f.pr_off = c_pr + nrounds_;
-      f.pr_cf = c_pr + 2 * nrounds_;
-      f.pr_len = c_pr + 3 * nrounds_;
-      f.nrounds = nrounds_;
-      f.npairs = npairs_;
-      f.nc = c_nc;
-      f.Rc = c_Rc;
-      f.dec = s_dec.p;
-      f.decbit = s_decbit.p;
-      f.Lc = c_Lc;
-      f.ncalls = ncalls_;
-      f.lcr_start = lcr;
-      f.LCR = s_LCR.p;
-      f.clast = s_clast.p;
-      f.flags = c_flags;
-      f.out = hdr;
-      f.nout = 8 + ncalls_;
-      return f;
-    };
-    bool otail = false;  // the order's stages from the call's bucket on ran as one launch
-    tp[1] = now_ns();
-    // ---- DecideFame windows (host enumeration of (round, call) pairs) + control block ----
-    std::vector<int32_t> pr_round, pr_off, pr_cf, pr_len;
-    int npairs = 0, nrounds = 0;
-    int64_t nslot = 0;
-    int lcr_new = lcr, c_set = -1;
-    // every round's window reaching the last call (always so for one call: the
-    // online path) cannot widen: the coverage flags stay on the device, and the new
-    // LastConsensusRound comes back with the batch's closing readback
-    bool lcr_dev = false;
-    const int i_lo = lcr + 1;
-    const int i_hi = Rc[ncalls - 1] - 2;  // processed rounds: i <= R_c - 2
-    // speculative fame window: calls up to R_c <= i + 2 + SPEC, widened when a round
-    // stays undecided past it (narrower windows re-dispatch more often: slower)
-    // Selective widening (N >= 192 a multiple of 64, no split or record; smaller N pay
-    // more for the passes' round trips than the fame work they save): every window starts
-    // at SPEC = 1 and only the rounds whose decision came past their window are
-    // widened and re-decided (their new pairs alone; the other rounds' decisions are
-    // moved to the new layout).  At 256/10M 517 of 2,836 rounds go to SPEC = 2 and 6
-    // of those to 4; a uniform SPEC = 3 decides twice the pairs.
-    const bool selective = do_fame && N % 64 == 0 && N >= 192 && !split_on() && !rec_on && ncalls > 1;
+  FameCall fame_call_args(const Batch& b, int32_t* hdr) const {
+    const int nrounds = b.w.nrounds();
+    FameCall f{};
+    f.pr_round = c_pr;
+    f.pr_off = c_pr + nrounds;
+    f.pr_cf = c_pr + 2 * nrounds;
+    f.pr_len = c_pr + 3 * nrounds;
+    f.nrounds = nrounds;
+    f.npairs = b.w.npairs;
+    f.nc = c_nc;
+    f.Rc = c_Rc;
+    f.dec = s_dec.p;
+    f.decbit = s_decbit.p;
+    f.Lc = c_Lc;
+    f.ncalls = b.ncalls;
+    f.lcr_start = lcr;
+    f.LCR = s_LCR.p;
+    f.clast = s_clast.p;
+    f.flags = c_flags;
+    f.out = hdr;
+    f.nout = (int)b.out.header();
+    return f;
+  }
+
+  // DecideFame's single-block launch that waited for the order's, on its own after all
+  void launch_pending_fame(Batch& b) {
+    if (!b.fame_pending) return;
+    KLAUNCH((k_fame_call<16, 1, true>), dim3(1), dim3(1024), 0, st, tables(), *b.fame_pending);
+    b.fame_pending.reset();
+  }
+
+  // DecideFame: plan the (round, call) windows on the host, upload the control block,
+  // decide, scan for the new LastConsensusRound; widen and go again while a round stays
+  // undecided past its window.
+  // Speculative fame window: calls up to R_c <= i + 2 + SPEC, widened when a round
+  // stays undecided past it (narrower windows re-dispatch more often: slower).
+  // Selective widening (N >= 192 a multiple of 64, no split or record; smaller N pay
+  // more for the passes' round trips than the fame work they save): every window starts
+  // at SPEC = 1 and only the rounds whose decision came past their window are
+  // widened and re-decided (their new pairs alone; the other rounds' decisions are
+  // moved to the new layout).  At 256/10M 517 of 2,836 rounds go to SPEC = 2 and 6
+  // of those to 4; a uniform SPEC = 3 decides twice the pairs.
+  void decide_fame(Batch& b) {
+    const Tables t = tables();
+    const int ncalls = b.ncalls;
+    b.lcr_new = lcr;
+    const bool selective = b.do_fame && N % 64 == 0 && N >= 192 && !split_on() && !rec_on && ncalls > 1;
     std::vector<int> spec_r;
-    std::vector<int32_t> old_off, old_len;
+    hge_plan::FameWindows old;  // a widening pass: the layout it widens
     for (int SPEC = selective ? 1 : 3, iter = 0;; SPEC *= 2, iter++) {
-      pr_round.clear();
-      pr_off.clear();
-      pr_cf.clear();
-      pr_len.clear();
-      npairs = 0;
-      if (do_fame) {
-        int cfp = 0;
-        for (int i = i_lo; i <= i_hi; i++) {
-          while (cfp < ncalls && Rc[cfp] < i + 2) cfp++;
-          if (cfp >= ncalls) break;
-          const int k = (int)pr_round.size();
-          if (selective && iter == 0) spec_r.push_back(SPEC);
-          const int sp = selective ? spec_r.at(k) : SPEC;
-          // last call with R_c <= i + 2 + SPEC
-          int a = cfp, b = ncalls - 1;
-          while (a < b) {
-            int mid = (a + b + 1) / 2;
-            if (Rc[mid] <= i + 2 + sp) a = mid;
-            else b = mid - 1;
-          }
-          pr_round.push_back(i);
-          pr_off.push_back(npairs);
-          pr_cf.push_back(cfp);
-          pr_len.push_back(a - cfp + 1);
-          npairs += a - cfp + 1;
-        }
-      }
-      nrounds = (int)pr_round.size();
-      // control block: n_c (int64), R_c, L_c = -1, flags, the four window arrays,
-      // the round -> window map of the order pass
-      const size_t o_Rc = 2 * (size_t)ncalls, o_Lc = o_Rc + ncalls, o_fl = o_Lc + ncalls;
-      const size_t o_pr = o_fl + 4, o_pidx = o_pr + 4 * (size_t)nrounds;
-      const size_t o_sgo = o_pidx + nr;  // N <= 64: per-round segment capacity offsets
-      std::vector<int32_t>& cc = h_cctl;
       // a widening pass keeps the calls, R_c and their offsets (the round set is the
       // same): only the window arrays are rewritten and uploaded, L_c and the flags are
       // reset on the device (k_dec_relayout)
-      const bool part = selective && iter > 0;
-      if (!part) {
-        cc.assign(o_sgo + nr + 1, 0);
-        memcpy(cc.data(), calls.data(), 8 * (size_t)ncalls);
-        memcpy(&cc[o_Rc], Rc.data(), 4 * (size_t)ncalls);
-        std::fill(cc.begin() + o_Lc, cc.begin() + o_fl, -1);
-      }
-      if (nrounds) {
-        memcpy(&cc[o_pr], pr_round.data(), 4 * (size_t)nrounds);
-        memcpy(&cc[o_pr + nrounds], pr_off.data(), 4 * (size_t)nrounds);
-        memcpy(&cc[o_pr + 2 * nrounds], pr_cf.data(), 4 * (size_t)nrounds);
-        memcpy(&cc[o_pr + 3 * nrounds], pr_len.data(), 4 * (size_t)nrounds);
-      }
-      for (int q = 0; q < nr; q++) cc[o_pidx + q] = -1;
-      for (int k = 0; k < nrounds; k++) {
-        const int i = pr_round[k];
-        if (i >= rr_lo && i < rr_lo + nr) cc[o_pidx + (i - rr_lo)] = k;
-      }
-      // a round's segments start at call 0, at a witness arrival (<= N distinct
-      // calls), at the window start or at a processed call of its fame window
-      nslot = 0;
-      for (int q = 0; q < nr; q++) {
-        cc[o_sgo + q] = (int32_t)nslot;
-        const int k = cc[o_pidx + q];
-        nslot += N + 2 + (k >= 0 ? pr_len[k] : 0);
-      }
-      cc[o_sgo + nr] = (int32_t)std::min<int64_t>(nslot, INF32);
-      if (part) {
-        h2d(s_cctl.p + o_pr, cc.data() + o_pr, 4 * (cc.size() - o_pr));
+      const bool widening = selective && iter > 0;
+      if (!b.do_fame) b.w = hge_plan::FameWindows();
+      else if (widening) b.w = hge_plan::plan_fame_windows(b.Rc, lcr, spec_r);
+      else b.w = hge_plan::plan_fame_windows(b.Rc, lcr, SPEC);
+      if (selective && iter == 0) spec_r.assign(b.w.nrounds(), SPEC);
+      const hge_plan::FameWindows& w = b.w;
+      const int nrounds = w.nrounds(), npairs = w.npairs;
+      b.ctl = hge_plan::ctl_layout(ncalls, nrounds, b.nr);
+      b.nslot = hge_plan::fill_ctl(h_cctl, b.ctl, b.calls, b.Rc, w, b.rr_lo, N, widening);
+      if (widening) {
+        h2d(s_cctl.p + b.ctl.pr, h_cctl.data() + b.ctl.pr, 4 * (b.ctl.total - b.ctl.pr));
       } else {
-        s_cctl.need(cc.size());
-        h2d(s_cctl.p, cc.data(), 4 * cc.size());
+        s_cctl.need(b.ctl.total);
+        h2d(s_cctl.p, h_cctl.data(), 4 * b.ctl.total);
       }
-      c_nc = (int64_t*)s_cctl.p;
-      c_Rc = s_cctl.p + o_Rc;
-      c_Lc = s_cctl.p + o_Lc;
-      c_flags = s_cctl.p + o_fl;
-      c_pr = s_cctl.p + o_pr;
-      c_pidx = s_cctl.p + o_pidx;
-      c_sgo = s_cctl.p + o_sgo;
+      bind_ctl(b.ctl);
       if (nrounds == 0) break;
-      if (!(selective && iter > 0)) s_dec.need((size_t)npairs * N);  // (a widening moves them first)
+      if (!widening) s_dec.need((size_t)npairs * N);  // (a widening moves them first)
       s_decbit.need(npairs);
       s_LCR.need(ncalls);
       s_clast.need(nrounds);
       bool full = true;
-      for (int k = 0; k < nrounds && full; k++) full = pr_cf[k] + pr_len[k] == ncalls;
+      for (int k = 0; k < nrounds && full; k++) full = w.cf[k] + w.len[k] == ncalls;
       // one call at N < 64 (an online call): decide, timeline, LCR and the results
       // header in one single-block launch (their grids were a block or two each)
       const int Gf = group_lanes();
@@ -2084,85 +2154,37 @@ struct hge_engine {
       if (one && N >= 64) {
         // the pairs by k_fame_decide_blk, then the timeline, LCR and the results header
         // in one single-block launch (in place of k_fame_timeline_g, k_lcr_scan, k_out_init)
-        s_out.need(o_tx0 + 2 * (size_t)ntxb0);
-        int32_t* hdr = s_out.p;
-        fame_dispatch(0, t, nrounds, npairs, ncalls, &pr_round, &pr_off, true);
-        const FameCall fc = fame_call_args(nrounds, npairs, ncalls, hdr);
-        switch (NW) {
-#define FTAIL(B)                                                                                      \
-  case B:                                                                                             \
-    KLAUNCH((k_fame_call<64, B, false>), dim3(1), dim3(1024), 0, st, t, fc);                           \
-    break;
-          FTAIL(1)
-          FTAIL(2)
-          FTAIL(3)
-          FTAIL(4)
-#undef FTAIL
-          default:
-            throw EngineError(HGE_ERR_INTERNAL, "unsupported N");
-        }
-        hdr_done = true;
+        s_out.need(b.out.total());
+        fame_decide(t, w, npairs, false);
+        const FameCall fc = fame_call_args(b, s_out.p);
+        KLAUNCH_NW(NW, NW_PATC, k_fame_call, 64, false, dim3(1), dim3(1024), 0, st, t, fc);
+        b.hdr_done = true;
         x_iter++;
-        lcr_dev = true;
+        b.lcr_dev = true;
         break;
       }
       if (one && N < 64 && (int64_t)npairs * N <= 8192) {
-        s_out.need(o_tx0 + 2 * (size_t)ntxb0);
-        int32_t* hdr = s_out.p;
-        fc_pend = fame_call_args(nrounds, npairs, ncalls, hdr);
-#define FCALL(GG) KLAUNCH((k_fame_call<GG, 1, true>), dim3(1), dim3(1024), 0, st, t, fc_pend);
-        if (Gf == 16) {
-          // launched with the order's stages when they run as one block (k_consensus_call)
-          fame_deferred = true;
-        } else if (Gf == 32) {
-          FCALL(32)
-        } else {
-          FCALL(64)
+        s_out.need(b.out.total());
+        b.fame_pending = fame_call_args(b, s_out.p);
+        // G = 16: launched with the order's stages when they run as one block (k_consensus_call)
+        if (Gf == 32) {
+          KLAUNCH((k_fame_call<32, 1, true>), dim3(1), dim3(1024), 0, st, t, *b.fame_pending);
+          b.fame_pending.reset();
+        } else if (Gf == 64) {
+          KLAUNCH((k_fame_call<64, 1, true>), dim3(1), dim3(1024), 0, st, t, *b.fame_pending);
+          b.fame_pending.reset();
         }
-#undef FCALL
-        hdr_done = true;
+        b.hdr_done = true;
         x_iter++;
-        lcr_dev = true;
+        b.lcr_dev = true;
         break;
       }
-      if (selective && iter > 0) {
-        // the previous layout's decisions moved, then the widened rounds' new pairs
-        s_dec2.need((size_t)npairs * N);
-        std::vector<int32_t> rel(2 * (size_t)nrounds);
-        std::vector<int32_t> plist;
-        for (int k = 0; k < nrounds; k++) {
-          rel[k] = old_off[k];
-          rel[nrounds + k] = old_len[k];
-          for (int q = old_len[k]; q < pr_len[k]; q++) plist.push_back(pr_off[k] + q);
-        }
-        s_relay.need(rel.size() + plist.size() + 1);
-        h2d(s_relay.p, rel.data(), 4 * rel.size());
-        if (!plist.empty()) h2d(s_relay.p + rel.size(), plist.data(), 4 * plist.size());
-        KLAUNCH(k_dec_relayout, dim3(nrounds), dim3(256), 0, st, (const uint8_t*)s_dec.p, s_dec2.p,
-                (const int32_t*)s_relay.p, (const int32_t*)(s_relay.p + nrounds), (const int32_t*)(c_pr + nrounds),
-                N, c_Lc, ncalls, c_flags);
-        std::swap(s_dec, s_dec2);
-        if (!plist.empty()) {
-          switch (NW) {
-#define XCASE(B)                                                                                      \
-  case B:                                                                                             \
-    KLAUNCH((k_fame_decide_blk<B>), dim3((unsigned)plist.size()), dim3(N), 0, st, t, c_pr, c_pr + nrounds, \
-            c_pr + 2 * nrounds, nrounds, 0, npairs, c_nc, c_Rc, s_dec.p,                              \
-            (const int32_t*)(s_relay.p + rel.size()));                                                \
-    break;
-            XCASE(1)
-            XCASE(2)
-            XCASE(3)
-            XCASE(4)
-#undef XCASE
-            default:
-              throw EngineError(HGE_ERR_INTERNAL, "unsupported N");
-          }
-        }
+      if (widening) {
+        widen_decisions(t, old, w, ncalls);
         // the timeline over the whole layout again
-        fame_dispatch(0, t, nrounds, 0, ncalls, &pr_round, &pr_off);
+        fame_decide(t, w, 0);
       } else {
-        fame_dispatch(0, t, nrounds, npairs, ncalls, &pr_round, &pr_off);
+        fame_decide(t, w, npairs);
       }
       if (rec_on && !split_on()) {
         rec_dec.emplace_back((size_t)npairs * N);
@@ -2174,7 +2196,7 @@ struct hge_engine {
               c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, s_clast.p, c_flags,
               selective ? s_rfail.p : (int32_t*)nullptr);
       if (full) {
-        lcr_dev = true;
+        b.lcr_dev = true;
         break;
       }
       int32_t fl[3];
@@ -2183,408 +2205,410 @@ struct hge_engine {
       readback(fl, c_flags, 3);
       if (fl[0]) {  // a round stayed undecided past its window: widen (those rounds only)
         if (selective) {
-          old_off = pr_off;
-          old_len = pr_len;
           for (int k = 0; k < nrounds; k++)
             if (rf[k]) spec_r[k] *= 2;
+          old = std::move(b.w);
         }
         continue;
       }
-      lcr_new = fl[1];
-      if (lcr_new > lcr) c_set = fl[2];
+      b.lcr_new = fl[1];
+      if (b.lcr_new > lcr) b.c_set = fl[2];
       break;
     }
+  }
+  // a selective widening pass: the previous layout's decisions moved into the new one,
+  // then the widened rounds' new pairs decided
+  void widen_decisions(const Tables& t, const hge_plan::FameWindows& old, const hge_plan::FameWindows& w, int ncalls) {
+    const int nrounds = w.nrounds();
+    s_dec2.need((size_t)w.npairs * N);
+    std::vector<int32_t> rel(2 * (size_t)nrounds);
+    std::vector<int32_t> plist;
+    for (int k = 0; k < nrounds; k++) {
+      rel[k] = old.off[k];
+      rel[nrounds + k] = old.len[k];
+      for (int q = old.len[k]; q < w.len[k]; q++) plist.push_back(w.off[k] + q);
+    }
+    s_relay.need(rel.size() + plist.size() + 1);
+    h2d(s_relay.p, rel.data(), 4 * rel.size());
+    if (!plist.empty()) h2d(s_relay.p + rel.size(), plist.data(), 4 * plist.size());
+    KLAUNCH(k_dec_relayout, dim3(nrounds), dim3(256), 0, st, (const uint8_t*)s_dec.p, s_dec2.p,
+            (const int32_t*)s_relay.p, (const int32_t*)(s_relay.p + nrounds), (const int32_t*)(c_pr + nrounds),
+            N, c_Lc, ncalls, c_flags);
+    std::swap(s_dec, s_dec2);
+    if (!plist.empty())
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3((unsigned)plist.size()), dim3(N), 0, st, t, c_pr,
+                 c_pr + nrounds, c_pr + 2 * nrounds, nrounds, 0, w.npairs, c_nc, c_Rc, s_dec.p,
+                 (const int32_t*)(s_relay.p + rel.size()));
+  }
 
-    tp[2] = now_ns();
-    // ---- DecideRoundReceived / FindOrder ----
-    bool got_order = false;
-    // results block: counters | per-call counts | order | per-block transaction sums
-    const size_t o_tx = o_tx0;
-    const int ntxb = ntxb0;
-    s_out.need(o_tx + 2 * (size_t)ntxb);
-    int32_t* o_cnt = s_out.p;  // [0] received [1] undetermined [2] LCR events [4..5] tx
-    int32_t* o_cc = s_out.p + 8;
-    int32_t* o_ids = s_out.p + 8 + ncalls;
-    // a replay's sorts write the order straight into the pinned order buffer (host
-    // memory mapped into the device: the writes cross PCIe while the later buckets
-    // sort; no copy after the replay)
-    const bool direct = lazy_order && !order_out && !spl && pin_ord_dev;
-    int32_t* ids_dst = o_ids;
-    bool wrote_direct = false;  // (only the bucket sorts below write there; other paths write o_ids)
-    unsigned long long* o_ntx = (unsigned long long*)(s_out.p + 4);
-    // the results header zeroed, with the new LastConsensusRound (o_cnt[3]) when the
-    // device holds it (one launch in place of a memset and a copy)
-    // (folded into k_visibility's launch when that runs)
-    const int32_t* lcr_src = lcr_dev ? (const int32_t*)(c_flags + 1) : (const int32_t*)nullptr;
+  // the single-block order kernel's arguments (k_order_call, k_consensus_call, and
+  // k_consensus_dyn, which fills the round scalars and control pointers itself), with
+  // the scratch they name
+  OrderCall order_call(const Batch& b, int front) {
+    const int ncalls = b.ncalls, ncand = b.ncand;
+    s_recv.need(ncand);
+    s_rr.need(ncand);
+    s_cts.need(ncand);
+    s_fund.need(ncand);
+    s_upos.need(ncand);
+    s_bpos.need(2 * (size_t)ncalls + 2);
+    s_und2.need(d_und.n);
+    s_keys.need((size_t)ncand * sizeof(OKey));
+    s_keys2.need((size_t)ncand * sizeof(OKey));
+    OrderCall oc{};
+    oc.si = b.si;
+    oc.rr_lo = b.rr_lo;
+    oc.nr = b.nr;
+    oc.segoff = c_sgo;
+    oc.segcnt = s_segcnt.p;
+    oc.seg_call = s_segcall.p;
+    oc.seg_round = s_seground.p;
+    oc.seg_dec = s_segdec.p;
+    oc.seg_fws = s_segfws.p;
+    oc.theta = s_theta.p;
+    oc.cand = b.cand;
+    oc.ncand = ncand;
+    oc.R_last = b.R_last;
+    oc.recv = s_recv.p;
+    oc.rr = s_rr.p;
+    oc.cts = s_cts.p;
+    oc.cnt = out_counts();
+    oc.bpos = s_bpos.p;
+    oc.total = out_word(hge_plan::ResultsLayout::kReceived);
+    oc.blist = s_bpos.p + ncalls;
+    oc.nblist = s_bpos.p + 2 * ncalls;
+    oc.f_und = s_fund.p;
+    oc.upos = s_upos.p;
+    oc.nund = out_word(hge_plan::ResultsLayout::kUndetermined);
+    oc.und_out = s_und2.p;
+    oc.k1 = (OKey*)s_keys.p;
+    oc.k2 = (OKey*)s_keys2.p;
+    oc.ev_rr = d_rr.p;
+    oc.ev_cts = d_cts.p;
+    oc.ntx = out_tx(b);
+    oc.ntxb = b.out.ntxb;
+    oc.ids = out_ids(b);
+    oc.pr = c_pr;
+    oc.nrounds = b.do_fame ? b.w.nrounds() : 0;
+    oc.clast = s_clast.p;
+    oc.dec = s_dec.p;
+    oc.nc = c_nc;
+    oc.flags = c_flags;
+    oc.lcr_old = lcr;
+    oc.n_lo = (int)std::min<int64_t>(b.calls[0], n_coords);
+    oc.n1 = (int)n_coords;
+    oc.lcre_out = out_word(hge_plan::ResultsLayout::kLcrEvents);
+    oc.front = front;
+    return oc;
+  }
+
+  // the frontier rows transposed (WLA) for the batch's rounds: theta (N > 64) and the
+  // median (N > 16) read them
+  void ensure_wla(Batch& b) {
+    if (b.wla_done || N <= 16 || b.R_last <= b.rr_lo) return;
+    b.wla_done = true;
+    d_WLA.need((size_t)Rcap * N * N);
+    if (N > 64 && !wide32) d_WLR.need((size_t)Rcap * N * N);
+    const Tables tw = tables();
+    KLAUNCH(k_witness_la, dim3(div_up(N, 64), div_up(N, 64), b.R_last - b.rr_lo), dim3(256), 0, st, tw, b.rr_lo);
+  }
+
+  // DecideRoundReceived: visibility, the rounds' segments with theta, round received and
+  // the median as their own grids -- or all of it and the rest of the order in one
+  // block (k_order_call / k_consensus_call: an online call at N <= 16).  Leaves s_recv.
+  void order_stages(Batch& b) {
+    const int ncalls = b.ncalls, ncand = b.ncand, nr = b.nr, nrounds = b.w.nrounds();
+    s_out.need(b.out.total());
     // an online call at N <= 16: the order's stages in one single-block launch
     // (k_order_call: segments, round received with its median, the call's bucket, the
     // undetermined list, keys, the sort, the persisted fame), with DecideFame's block
     // in front when it waited (k_consensus_call)
-    const bool ocall_pre = ord && nr > 0 && ncalls == 1 && calls[0] >= n_coords && commit && N <= 16 && !spl &&
-                           ncand <= SCAN_LDS && (int64_t)nr * group_lanes() <= 65536 &&
-                           (nrounds == 0 || lcr_dev) && !getenv("HGE_NO_ORDER_CALL");
-    if (fame_deferred && !ocall_pre) {
-      KLAUNCH((k_fame_call<16, 1, true>), dim3(1), dim3(1024), 0, st, t, fc_pend);
-      fame_deferred = false;
-    }
-    if (!(ord && nr > 0) && !hdr_done)
-      KLAUNCH(k_out_init, dim3(div_up(8 + ncalls, 256)), dim3(256), 0, st, s_out.p, 8 + ncalls, lcr_src);
-    // the single-block order kernel's arguments (k_order_call; front: the caller sets it)
-    auto order_call_args = [&](const SegInfo& si) {
+    const bool ocall = nr > 0 && ncalls == 1 && b.calls[0] >= n_coords && b.commit && N <= 16 && !b.spl &&
+                       ncand <= SCAN_LDS && (int64_t)nr * group_lanes() <= 65536 && (nrounds == 0 || b.lcr_dev) &&
+                       !getenv("HGE_NO_ORDER_CALL");
+    if (!ocall) launch_pending_fame(b);
+    if (nr == 0) {
+      // the results header zeroed, with the new LastConsensusRound when the device holds
+      // it (one launch in place of a memset and a copy)
+      if (!b.hdr_done) out_init(b);
       s_recv.need(ncand);
-      s_rr.need(ncand);
-      s_cts.need(ncand);
-      s_fund.need(ncand);
-      s_upos.need(ncand);
-      s_bpos.need(2 * (size_t)ncalls + 2);
-      s_und2.need(d_und.n);
-      s_keys.need((size_t)ncand * sizeof(OKey));
-      s_keys2.need((size_t)ncand * sizeof(OKey));
-      OrderCall oc{};
-      oc.si = si;
-      oc.rr_lo = rr_lo;
-      oc.nr = nr;
-      oc.segoff = c_sgo;
-      oc.segcnt = s_segcnt.p;
-      oc.seg_call = s_segcall.p;
-      oc.seg_round = s_seground.p;
-      oc.seg_dec = s_segdec.p;
-      oc.seg_fws = s_segfws.p;
-      oc.theta = s_theta.p;
-      oc.cand = cand;
-      oc.ncand = ncand;
-      oc.R_last = R_last;
-      oc.recv = s_recv.p;
-      oc.rr = s_rr.p;
-      oc.cts = s_cts.p;
-      oc.cnt = o_cc;
-      oc.bpos = s_bpos.p;
-      oc.total = o_cnt;
-      oc.blist = s_bpos.p + ncalls;
-      oc.nblist = s_bpos.p + 2 * ncalls;
-      oc.f_und = s_fund.p;
-      oc.upos = s_upos.p;
-      oc.nund = o_cnt + 1;
-      oc.und_out = s_und2.p;
-      oc.k1 = (OKey*)s_keys.p;
-      oc.k2 = (OKey*)s_keys2.p;
-      oc.ev_rr = d_rr.p;
-      oc.ev_cts = d_cts.p;
-      oc.ntx = (unsigned long long*)(s_out.p + o_tx);
-      oc.ntxb = ntxb;
-      oc.ids = o_ids;
-      oc.pr = c_pr;
-      oc.nrounds = do_fame ? nrounds : 0;
-      oc.clast = s_clast.p;
-      oc.dec = s_dec.p;
-      oc.nc = c_nc;
-      oc.flags = c_flags;
-      oc.lcr_old = lcr;
-      oc.n_lo = (int)std::min<int64_t>(calls[0], n_coords);
-      oc.n1 = (int)n_coords;
-      oc.lcre_out = o_cnt + 2;
-      return oc;
-    };
-    // one call's bucket, undetermined list, keys, sort and persisted fame as one
-    // single-block launch at any N (k_order_call, front = 0) when the order's first
-    // stages ran as their own grids
-    const bool otail_ok = ord && commit && ncalls == 1 && !spl && ncand <= SCAN_LDS &&
-                          (!do_fame || nrounds == 0 || lcr_dev) && !getenv("HGE_NO_ORDER_CALL");
-    SegInfo si_tail{};
-    if (ord) {
-      if (nr > 0) {
-        SegInfo si;
-        si.pr_index = c_pidx;
-        if (nrounds > 0) {
-          si.pr_off = c_pr + nrounds;
-          si.pr_cf = c_pr + 2 * nrounds;
-          si.pr_len = c_pr + 3 * nrounds;
-          si.clast = s_clast.p;
-          si.dec = s_dec.p;
-        } else {
-          si.pr_off = si.pr_cf = si.pr_len = si.clast = nullptr;
-          si.dec = nullptr;
-        }
-        si_tail = si;
-        s_segcnt.need(nr);
-        // first call at which each event is visible (arrivals, round received); one call
-        // that sees every event (an online call) needs no table: 0 for all, and the
-        // header is zeroed alone (a table of every event per call grew with the stream)
-        vis_all = ncalls == 1 && calls[0] >= n_coords;
-        if (vis_all) {
-          if (!hdr_done)
-            KLAUNCH(k_out_init, dim3(div_up(8 + ncalls, 256)), dim3(256), 0, st, s_out.p, 8 + ncalls, lcr_src);
-        } else {
-          s_vis.need(std::max<int64_t>(n_coords, 1));
-          KLAUNCH(k_visibility, dim3(div_up(n_coords, 256) + div_up(8 + ncalls, 256)), dim3(256), 0, st,
-                  (const int64_t*)c_nc, ncalls, (int)n_coords, s_vis.p, s_out.p, 8 + ncalls, lcr_src);
-        }
-        const int32_t* visp = vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p;
-        // one pass into per-round capacity slots (no count round trip); theta inline
-        // for N <= 64, by k_seg_theta_wide above
-        const int G = group_lanes();
-        const size_t ns = (size_t)std::max<int64_t>(nslot, 1);
-        s_segcall.need(ns);
-        s_seground.need(ns);
-        s_segdec.need(ns);
-        s_segfws.need(ns * NW);
-        s_theta.need(ns * N);
-        segoff_p = c_sgo;
-        ocall = ocall_pre;
-        if (ocall) {
-          OrderCall oc = order_call_args(si);
-          oc.front = 1;
-          if (fame_deferred) {
-            KLAUNCH(k_consensus_call<16>, dim3(1), dim3(1024), 0, st, t, fc_pend, oc);
-            fame_deferred = false;
-          } else {
-            KLAUNCH(k_order_call<16>, dim3(1), dim3(1024), 0, st, t, oc);
-          }
-          std::swap(d_und, s_und2);
-          got_order = true;
-        }
-#define SEG1(GG, SPL)                                                                              \
-  KLAUNCH((k_segments_1p<GG, SPL>), dim3(div_up((int64_t)nr * GG, 256)), dim3(256), 0, st, t,      \
-          rr_lo, nr, ncalls, visp, si, (const int32_t*)c_sgo, s_segcnt.p,                          \
-          s_segcall.p, s_seground.p, s_segdec.p, s_segfws.p, s_theta.p);
-#define THW(B)                                                                                     \
-  if (wide32)                                                                                      \
-    KLAUNCH(k_seg_theta32<B>, dim3(std::min(nr, 4096)), dim3(256), 0, st, t,                       \
-            (const int32_t*)s_seground.p, (const int32_t*)c_sgo, (const int32_t*)s_segcnt.p, nr,   \
-            (const uint64_t*)s_segfws.p, s_theta.p);                                               \
-  else                                                                                             \
-    KLAUNCH(k_seg_theta_wide<B>, dim3(std::min(nr, 4096), nr < 64 ? 8 : 2), dim3(1024), 0, st, t,  \
-            (const int32_t*)s_seground.p, (const int32_t*)c_sgo, (const int32_t*)s_segcnt.p, nr,   \
-            (const uint64_t*)s_segfws.p, s_theta.p, dbg_p());
-        // the frontier rows transposed (WLA) for the batch's rounds: theta (N > 64) and
-        // the median (N > 16) read them
-        const bool wla = N > 16 && R_last > rr_lo && !ocall;
-        if (wla) {
-          d_WLA.need((size_t)Rcap * N * N);
-          if (N > 64 && !wide32) d_WLR.need((size_t)Rcap * N * N);
-          Tables tw = tables();
-          KLAUNCH(k_witness_la, dim3(div_up(N, 64), div_up(N, 64), R_last - rr_lo), dim3(256), 0, st, tw,
-                  rr_lo);
-          t = tables();
-        }
-        if (ocall) {
-          // (k_order_call above)
-        } else if (G == 16) {
-          SEG1(16, 1)
-        } else if (G == 32) {
-          SEG1(32, 1)
-        } else if (NW == 1) {
-          SEG1(64, 1)
-        } else if (NW == 2) {
-          SEG1(64, 2)
-          THW(2)
-        } else if (NW == 3) {
-          SEG1(64, 3)
-          THW(3)
-        } else {
-          SEG1(64, 4)
-          THW(4)
-        }
-#undef SEG1
-#undef THW
-        if (getenv("HGE_SEG_DEBUG")) {  // diagnostics: the segments theta walks this batch
-          std::vector<int32_t> sc(nr);
-          readback(sc.data(), s_segcnt.p, nr);
-          int tot = 0, mx = 0;
-          for (int v : sc) {
-            tot += v;
-            mx = std::max(mx, v);
-          }
-          fprintf(stderr, "[hge seg] calls %d rounds %d segments %d max per round %d\n", ncalls, nr, tot, mx);
-          if (dbg_on && s_dbg.p) {
-            uint64_t v[16];
-            readback(v, s_dbg.p, 16);
-            fprintf(stderr, "[hge theta] segments %llu cycles: rows %llu staging %llu bisection %llu\n",
-                    (unsigned long long)v[15], (unsigned long long)v[12], (unsigned long long)v[13],
-                    (unsigned long long)v[14]);
-          }
-        }
-        // round-received per candidate
-        if (!ocall) {
-          s_recv.need(ncand);
-          s_rr.need(ncand);
-          s_cts.need(ncand);
-          recv_dispatch(t, cand, ncand, ncalls, rr_lo, R_last, fresh_und, wla);
-        }
-      } else {
-        s_recv.need(ncand);
-        HIPCHK(hipMemsetAsync(s_recv.p, 0xFF, 4 * ncand, st));
-      }
-      if (spl) {  // keep what this part's calls receive (k_split_filter)
-        const int p = sp.part;
-        const int32_t guard = p + 1 < sp.nparts ? (int32_t)sp.clo[p + 1] : INT32_MIN;
-        HIPCHK(hipMemsetAsync(s_small.p + 8, 0, 4, st));
-        KLAUNCH(k_split_filter, dim3(div_up(ncand, 256)), dim3(256), 0, st, (const int32_t*)cand, ncand,
-                s_recv.p, sp.cb[p], sp.cb[p + 1] - 1, guard, s_small.p + 8);
-      }
-      // compaction + the order as call buckets (the received count stays on the
-      // device: o_cnt[0])
-      if (!ocall && otail_ok) {
-        OrderCall oc = order_call_args(si_tail);
-        oc.front = 0;
-        KLAUNCH(k_order_call<16>, dim3(1), dim3(1024), 0, st, t, oc);
-        std::swap(d_und, s_und2);
-        got_order = true;
-        otail = true;
-      } else if (!ocall) {
-        s_fund.need(ncand);
-        s_upos.need(ncand);
-        s_rr.need(ncand);
-        s_cts.need(ncand);
-        // an online call's flags, buckets and undetermined list: one launch (k_recv_list_und below)
-        const bool rlu = commit && ncand <= 16384 && ncalls <= 8;
-        if (!rlu)
-          KLAUNCH(k_recv_flags, dim3(div_up(ncand, 256)), dim3(256), 0, st, s_recv.p, ncand,
-                  (int32_t*)nullptr, s_fund.p, commit ? 1 : 0, commit ? o_cc : (int32_t*)nullptr);
-        if (!commit)
-          KLAUNCH(k_set_rr, dim3(div_up(ncand, 256)), dim3(256), 0, st, t, cand, ncand, s_recv.p,
-                  s_rr.p, s_cts.p, d_rr.p, d_cts.p, o_ntx, 0);
-        if (commit) {
-          s_bpos.need(2 * (size_t)ncalls + 2);
-          int32_t* blist = s_bpos.p + ncalls;     // non-empty buckets
-          int32_t* nblist = s_bpos.p + 2 * ncalls;  // their count
-          // a small candidate set: the undetermined list's scan and scatter ride with the
-          // call buckets (k_list_und; the list swap below is the same)
-          const bool lu = ncand <= 16384;
-          s_und2.need(d_und.n);
-          if (rlu)
-            KLAUNCH(k_recv_list_und, dim3(2), dim3(1024), 0, st, (const int32_t*)s_recv.p, (int)ncand, o_cc, ncalls,
-                    s_bpos.p, o_cnt, blist, nblist, s_fund.p, s_upos.p, o_cnt + 1, cand, s_und2.p);
-          else if (lu)
-            KLAUNCH(k_list_und, dim3(2), dim3(1024), 0, st, (const int32_t*)o_cc, ncalls, s_bpos.p, o_cnt, blist,
-                    nblist, (const int32_t*)s_fund.p, s_upos.p, (int)ncand, o_cnt + 1, cand, s_und2.p);
-          else
-            KLAUNCH(k_bucket_list, dim3(1), dim3(1024), 0, st, (const int32_t*)o_cc, ncalls, s_bpos.p,
-                    o_cnt, blist, nblist);
-          s_keys.need((size_t)ncand * sizeof(OKey));
-          s_keys2.need((size_t)ncand * sizeof(OKey));
-          OKey* k1 = (OKey*)s_keys.p;
-          OKey* k2 = (OKey*)s_keys2.p;
-          KLAUNCH(k_bucket_keys, dim3(div_up(ncand, 256)), dim3(256), 0, st, t, cand, ncand, s_recv.p,
-                  s_rr.p, s_cts.p, s_bpos.p, k1, d_rr.p, d_cts.p,
-                  (unsigned long long*)(s_out.p + o_tx));
-          if (direct) {
-            ids_dst = pin_ord_dev;
-            wrote_direct = true;
-          }
-          if (ncalls <= 8) {
-            // a few buckets (an online call): one launch, each bucket to the path its size takes
-            KLAUNCH(k_bucket_sort_all, dim3(ncalls), dim3(1024), 0, st, (const int32_t*)s_bpos.p,
-                    (const int32_t*)o_cc, (const int32_t*)blist, (const int32_t*)nblist, k1, k2, ids_dst);
-          } else {
-            // buckets of 513 .. 2 * BIG_SORT keys in LDS (k_bucket_sort_big), the rest here
-            KLAUNCH(k_bucket_sort, dim3(std::min(ncalls, 2048)), dim3(256), 0, st,
-                    (const int32_t*)s_bpos.p, (const int32_t*)o_cc, (const int32_t*)blist,
-                    (const int32_t*)nblist, k1, k2, ids_dst, 1);
-            if (ncand > 512)  // (no bucket past 512 keys otherwise)
-              KLAUNCH(k_bucket_sort_big, dim3(std::min(ncalls, n_cu())), dim3(1024), 0, st,
-                      (const int32_t*)s_bpos.p, (const int32_t*)o_cc, (const int32_t*)blist,
-                      (const int32_t*)nblist, (const OKey*)k1, k2, ids_dst);
-          }
-          // new undetermined list (in candidate order), scattered into the spare list
-          // (same capacity) and swapped: no device copy
-          if (!lu) {
-            scan_large(s_fund.p, s_upos.p, ncand, o_cnt + 1);
-            KLAUNCH(k_scatter_und, dim3(div_up(ncand, 256)), dim3(256), 0, st, cand, ncand, s_fund.p, s_upos.p,
-                    s_und2.p);
-          }
-          std::swap(d_und, s_und2);
-          got_order = true;
-        }
-      }
+      HIPCHK(hipMemsetAsync(s_recv.p, 0xFF, 4 * ncand, st));
+      return;
     }
+    SegInfo& si = b.si;
+    si.pr_index = c_pidx;
+    if (nrounds > 0) {
+      si.pr_off = c_pr + nrounds;
+      si.pr_cf = c_pr + 2 * nrounds;
+      si.pr_len = c_pr + 3 * nrounds;
+      si.clast = s_clast.p;
+      si.dec = s_dec.p;
+    }
+    s_segcnt.need(nr);
+    // first call at which each event is visible (arrivals, round received); one call
+    // that sees every event (an online call) needs no table: 0 for all, and the
+    // header is zeroed alone (a table of every event per call grew with the stream)
+    vis_all = ncalls == 1 && b.calls[0] >= n_coords;
+    if (vis_all) {
+      if (!b.hdr_done) out_init(b);
+    } else {  // (the header's zeroing folded into k_visibility's launch)
+      const int nh = (int)b.out.header();
+      s_vis.need(std::max<int64_t>(n_coords, 1));
+      KLAUNCH(k_visibility, dim3(div_up(n_coords, 256) + div_up(nh, 256)), dim3(256), 0, st,
+              (const int64_t*)c_nc, ncalls, (int)n_coords, s_vis.p, s_out.p, nh, lcr_src(b));
+    }
+    const int32_t* visp = vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p;
+    // one pass into per-round capacity slots (no count round trip); theta inline
+    // for N <= 64, by k_seg_theta_wide past it
+    const size_t ns = (size_t)std::max<int64_t>(b.nslot, 1);
+    s_segcall.need(ns);
+    s_seground.need(ns);
+    s_segdec.need(ns);
+    s_segfws.need(ns * NW);
+    s_theta.need(ns * N);
+    segoff_p = c_sgo;
+    if (ocall) {
+      const OrderCall oc = order_call(b, 1);
+      if (b.fame_pending) {
+        KLAUNCH(k_consensus_call<16>, dim3(1), dim3(1024), 0, st, tables(), *b.fame_pending, oc);
+        b.fame_pending.reset();
+      } else {
+        KLAUNCH(k_order_call<16>, dim3(1), dim3(1024), 0, st, tables(), oc);
+      }
+      std::swap(d_und, s_und2);
+      b.got_order = true;
+      b.order_ran = OrderRan::CallFront;
+      if (getenv("HGE_SEG_DEBUG")) seg_debug(b);
+      return;
+    }
+    ensure_wla(b);
+    const Tables t = tables();
+    const int G = group_lanes();
+    const dim3 sgrid(div_up((int64_t)nr * G, 256));
+    const int32_t* sgo = c_sgo;
+    if (G == 16) {
+      KLAUNCH((k_segments_1p<16, 1>), sgrid, dim3(256), 0, st, t, b.rr_lo, nr, ncalls, visp, si, sgo, s_segcnt.p,
+              s_segcall.p, s_seground.p, s_segdec.p, s_segfws.p, s_theta.p);
+    } else if (G == 32) {
+      KLAUNCH((k_segments_1p<32, 1>), sgrid, dim3(256), 0, st, t, b.rr_lo, nr, ncalls, visp, si, sgo, s_segcnt.p,
+              s_segcall.p, s_seground.p, s_segdec.p, s_segfws.p, s_theta.p);
+    } else {
+      KLAUNCH_NW(NW, NW_PAT, k_segments_1p, 64, sgrid, dim3(256), 0, st, t, b.rr_lo, nr, ncalls, visp, si, sgo,
+                 s_segcnt.p, s_segcall.p, s_seground.p, s_segdec.p, s_segfws.p, s_theta.p);
+    }
+    if (NW > 1 && wide32) {
+      KLAUNCH_NW2(NW, NW_T, k_seg_theta32, dim3(std::min(nr, 4096)), dim3(256), 0, st, t,
+                  (const int32_t*)s_seground.p, (const int32_t*)c_sgo, (const int32_t*)s_segcnt.p, nr,
+                  (const uint64_t*)s_segfws.p, s_theta.p);
+    } else if (NW > 1) {
+      KLAUNCH_NW2(NW, NW_T, k_seg_theta_wide, dim3(std::min(nr, 4096), nr < 64 ? 8 : 2), dim3(1024), 0, st, t,
+                  (const int32_t*)s_seground.p, (const int32_t*)c_sgo, (const int32_t*)s_segcnt.p, nr,
+                  (const uint64_t*)s_segfws.p, s_theta.p, dbg_p());
+    }
+    if (getenv("HGE_SEG_DEBUG")) seg_debug(b);
+    // round-received per candidate
+    s_recv.need(ncand);
+    s_rr.need(ncand);
+    s_cts.need(ncand);
+    recv_dispatch(b);
+  }
+  // diagnostics (HGE_SEG_DEBUG): the segments theta walks this batch
+  void seg_debug(const Batch& b) {
+    std::vector<int32_t> sc(b.nr);
+    readback(sc.data(), s_segcnt.p, b.nr);
+    int tot = 0, mx = 0;
+    for (int v : sc) {
+      tot += v;
+      mx = std::max(mx, v);
+    }
+    fprintf(stderr, "[hge seg] calls %d rounds %d segments %d max per round %d\n", b.ncalls, b.nr, tot, mx);
+    if (dbg_on && s_dbg.p) {
+      uint64_t v[16];
+      readback(v, s_dbg.p, 16);
+      fprintf(stderr, "[hge theta] segments %llu cycles: rows %llu staging %llu bisection %llu\n",
+              (unsigned long long)v[15], (unsigned long long)v[12], (unsigned long long)v[13],
+              (unsigned long long)v[14]);
+    }
+  }
 
-    if (fame_deferred) throw EngineError(HGE_ERR_INTERNAL, "DecideFame's launch left pending");
-    // ---- persist fame / LCR ----
-    bool lcr_up = false;
-    if (do_fame && nrounds > 0 && !ocall && !otail) {
-      if (lcr_dev) {
-        // the persisted fame and RoundEvents(LCR - 1) as below (the new LCR and its
-        // call read on the device) in one launch
-        const int64_t nfrom = std::min<int64_t>(calls[0], n_coords);
-        const int nb_fp = (int)div_up((int64_t)nrounds * N, 256);
-        KLAUNCH(k_fame_persist_lcre, dim3(nb_fp + std::max(1, div_up(n_coords - nfrom, 256))), dim3(256), 0, st, t,
-                (const int32_t*)c_pr, (const int32_t*)(c_pr + nrounds), (const int32_t*)(c_pr + 2 * nrounds),
-                (const int32_t*)(c_pr + 3 * nrounds), nrounds, (const int32_t*)s_clast.p, (const uint8_t*)s_dec.p,
-                nb_fp, (const int64_t*)c_nc, (const int32_t*)c_flags, lcr, (int)nfrom, (int)n_coords, o_cnt + 2);
-      } else {
-        fame_dispatch(1, t, nrounds, npairs, ncalls);
-        if (lcr_new > lcr) {
-          // RoundEvents(lcr_new - 1) at call c_set: events of that round minus the
-          // ones inserted after that call
-          lcr_up = true;
-          const int r = lcr_new - 1;
-          if (r >= 0) {
-            const int64_t nfrom = std::min<int64_t>(calls[c_set], n_coords);
-            KLAUNCH(k_lcre, dim3(std::max(1, div_up(n_coords - nfrom, 256))), dim3(256), 0, st, t,
-                    (int)nfrom, (int)n_coords, r, o_cnt + 2);
-          }
-        }
+  // FindOrder from s_recv on: (a split part's filter,) the received events into their
+  // calls' buckets, keys, the sorts, the new undetermined list -- or one call's bucket,
+  // list, keys, sort and persisted fame as one single-block launch at any N
+  // (k_order_call, front = 0) when the order's first stages ran as their own grids.
+  // The received count stays on the device (the results header).
+  void bucket_and_sort(Batch& b) {
+    const int ncalls = b.ncalls, ncand = b.ncand;
+    int32_t* const cand = b.cand;
+    const Tables t = tables();
+    if (b.spl) {  // keep what this part's calls receive (k_split_filter)
+      const int p = sp.part;
+      const int32_t guard = p + 1 < sp.nparts ? (int32_t)sp.clo[p + 1] : INT32_MIN;
+      HIPCHK(hipMemsetAsync(s_small.p + 8, 0, 4, st));
+      KLAUNCH(k_split_filter, dim3(div_up(ncand, 256)), dim3(256), 0, st, (const int32_t*)cand, ncand,
+              s_recv.p, sp.cb[p], sp.cb[p + 1] - 1, guard, s_small.p + 8);
+    }
+    if (b.order_ran == OrderRan::CallFront) return;
+    const bool tail_ok = b.commit && ncalls == 1 && !b.spl && ncand <= SCAN_LDS &&
+                         (!b.do_fame || b.w.nrounds() == 0 || b.lcr_dev) && !getenv("HGE_NO_ORDER_CALL");
+    if (tail_ok) {
+      const OrderCall oc = order_call(b, 0);
+      KLAUNCH(k_order_call<16>, dim3(1), dim3(1024), 0, st, t, oc);
+      std::swap(d_und, s_und2);
+      b.got_order = true;
+      b.order_ran = OrderRan::CallTail;
+      return;
+    }
+    int32_t* const o_cnt = s_out.p;  // the results header: received [0], undetermined [1]
+    int32_t* const o_cc = out_counts();
+    int32_t* const o_und = out_word(hge_plan::ResultsLayout::kUndetermined);
+    s_fund.need(ncand);
+    s_upos.need(ncand);
+    s_rr.need(ncand);
+    s_cts.need(ncand);
+    // an online call's flags, buckets and undetermined list: one launch (k_recv_list_und below)
+    const bool rlu = b.commit && ncand <= 16384 && ncalls <= 8;
+    if (!rlu)
+      KLAUNCH(k_recv_flags, dim3(div_up(ncand, 256)), dim3(256), 0, st, s_recv.p, ncand,
+              (int32_t*)nullptr, s_fund.p, b.commit ? 1 : 0, b.commit ? o_cc : (int32_t*)nullptr);
+    if (!b.commit) {
+      KLAUNCH(k_set_rr, dim3(div_up(ncand, 256)), dim3(256), 0, st, t, cand, ncand, s_recv.p,
+              s_rr.p, s_cts.p, d_rr.p, d_cts.p, (unsigned long long*)out_word(hge_plan::ResultsLayout::kTx), 0);
+      return;
+    }
+    s_bpos.need(2 * (size_t)ncalls + 2);
+    int32_t* blist = s_bpos.p + ncalls;     // non-empty buckets
+    int32_t* nblist = s_bpos.p + 2 * ncalls;  // their count
+    // a small candidate set: the undetermined list's scan and scatter ride with the
+    // call buckets (k_list_und; the list swap below is the same)
+    const bool lu = ncand <= 16384;
+    s_und2.need(d_und.n);
+    if (rlu)
+      KLAUNCH(k_recv_list_und, dim3(2), dim3(1024), 0, st, (const int32_t*)s_recv.p, (int)ncand, o_cc, ncalls,
+              s_bpos.p, o_cnt, blist, nblist, s_fund.p, s_upos.p, o_und, cand, s_und2.p);
+    else if (lu)
+      KLAUNCH(k_list_und, dim3(2), dim3(1024), 0, st, (const int32_t*)o_cc, ncalls, s_bpos.p, o_cnt, blist,
+              nblist, (const int32_t*)s_fund.p, s_upos.p, (int)ncand, o_und, cand, s_und2.p);
+    else
+      KLAUNCH(k_bucket_list, dim3(1), dim3(1024), 0, st, (const int32_t*)o_cc, ncalls, s_bpos.p,
+              o_cnt, blist, nblist);
+    s_keys.need((size_t)ncand * sizeof(OKey));
+    s_keys2.need((size_t)ncand * sizeof(OKey));
+    OKey* k1 = (OKey*)s_keys.p;
+    OKey* k2 = (OKey*)s_keys2.p;
+    KLAUNCH(k_bucket_keys, dim3(div_up(ncand, 256)), dim3(256), 0, st, t, cand, ncand, s_recv.p,
+            s_rr.p, s_cts.p, s_bpos.p, k1, d_rr.p, d_cts.p, out_tx(b));
+    // a replay's sorts write the order straight into the pinned order buffer (host
+    // memory mapped into the device: the writes cross PCIe while the later buckets
+    // sort; no copy after the replay)
+    int32_t* ids_dst = out_ids(b);
+    if (lazy_order && !b.order_out && !b.spl && pin_ord_dev) {
+      ids_dst = pin_ord_dev;
+      b.wrote_direct = true;
+    }
+    if (ncalls <= 8) {
+      // a few buckets (an online call): one launch, each bucket to the path its size takes
+      KLAUNCH(k_bucket_sort_all, dim3(ncalls), dim3(1024), 0, st, (const int32_t*)s_bpos.p,
+              (const int32_t*)o_cc, (const int32_t*)blist, (const int32_t*)nblist, k1, k2, ids_dst);
+    } else {
+      // buckets of 513 .. 2 * BIG_SORT keys in LDS (k_bucket_sort_big), the rest here
+      KLAUNCH(k_bucket_sort, dim3(std::min(ncalls, 2048)), dim3(256), 0, st,
+              (const int32_t*)s_bpos.p, (const int32_t*)o_cc, (const int32_t*)blist,
+              (const int32_t*)nblist, k1, k2, ids_dst, 1);
+      if (ncand > 512)  // (no bucket past 512 keys otherwise)
+        KLAUNCH(k_bucket_sort_big, dim3(std::min(ncalls, n_cu())), dim3(1024), 0, st,
+                (const int32_t*)s_bpos.p, (const int32_t*)o_cc, (const int32_t*)blist,
+                (const int32_t*)nblist, (const OKey*)k1, k2, ids_dst);
+    }
+    // new undetermined list (in candidate order), scattered into the spare list
+    // (same capacity) and swapped: no device copy
+    if (!lu) {
+      scan_large(s_fund.p, s_upos.p, ncand, o_und);
+      KLAUNCH(k_scatter_und, dim3(div_up(ncand, 256)), dim3(256), 0, st, cand, ncand, s_fund.p, s_upos.p,
+              s_und2.p);
+    }
+    std::swap(d_und, s_und2);
+    b.got_order = true;
+  }
+
+  // the decided rounds' fame into the tables, and RoundEvents(LCR - 1) (k_order_call
+  // did both when it ran)
+  void persist_fame(Batch& b) {
+    const int nrounds = b.w.nrounds();
+    if (!b.do_fame || nrounds == 0 || b.order_ran != OrderRan::Stages) return;
+    const Tables t = tables();
+    int32_t* const lcre_out = out_word(hge_plan::ResultsLayout::kLcrEvents);
+    if (b.lcr_dev) {
+      // the persisted fame and RoundEvents(LCR - 1) as below (the new LCR and its
+      // call read on the device) in one launch
+      const int64_t nfrom = std::min<int64_t>(b.calls[0], n_coords);
+      const int nb_fp = (int)div_up((int64_t)nrounds * N, 256);
+      KLAUNCH(k_fame_persist_lcre, dim3(nb_fp + std::max(1, div_up(n_coords - nfrom, 256))), dim3(256), 0, st, t,
+              (const int32_t*)c_pr, (const int32_t*)(c_pr + nrounds), (const int32_t*)(c_pr + 2 * nrounds),
+              (const int32_t*)(c_pr + 3 * nrounds), nrounds, (const int32_t*)s_clast.p, (const uint8_t*)s_dec.p,
+              nb_fp, (const int64_t*)c_nc, (const int32_t*)c_flags, lcr, (int)nfrom, (int)n_coords, lcre_out);
+      return;
+    }
+    fame_persist(t, nrounds);
+    if (b.lcr_new > lcr) {
+      // RoundEvents(lcr_new - 1) at call c_set: events of that round minus the
+      // ones inserted after that call
+      b.lcr_up = true;
+      const int r = b.lcr_new - 1;
+      if (r >= 0) {
+        const int64_t nfrom = std::min<int64_t>(b.calls[b.c_set], n_coords);
+        KLAUNCH(k_lcre, dim3(std::max(1, div_up(n_coords - nfrom, 256))), dim3(256), 0, st, t,
+                (int)nfrom, (int)n_coords, r, lcre_out);
       }
     }
-    bool split_done = false;
-    if (spl && got_order) {  // the parts' ordered slices, joined in call order
-      split_commit(o_cnt, o_cc, o_ids, ntxb, (const unsigned long long*)(s_out.p + o_tx), order_out, counts_out);
-      got_order = false;
-      split_done = true;
-    }
-    tp[3] = now_ns();
-    // the batch's one closing round trip (read in place from the pinned arena); a
-    // replay's order stays in HBM (lazy: counters, per-call counts and transaction sums only)
-    const bool lazy = got_order && lazy_order && !order_out;
-    const size_t off = d2h_pinned(s_out.p, 4 * (got_order && !lazy ? o_tx + 2 * (size_t)ntxb : 8 + (size_t)ncalls));
-    const size_t off_tx = lazy ? d2h_pinned(s_out.p + o_tx, 4 * 2 * (size_t)ntxb) : 0;
+  }
+
+  // what a results block says, into the host state: the log (unless the ids were
+  // delivered to the pinned order buffer), ConsensusTransactions, the undetermined count
+  void commit_order(const hge_plan::Results& r, int ncalls, bool to_log, std::vector<int32_t>* order_out,
+                    std::vector<int64_t>* counts_out) {
+    if (to_log) consensus.insert(consensus.end(), r.ids, r.ids + r.nrecv);
+    ctx += (int64_t)r.ntx;
+    if (order_out) order_out->insert(order_out->end(), r.ids, r.ids + r.nrecv);
+    if (counts_out)
+      for (int c = 0; c < ncalls; c++) counts_out->push_back(r.counts[c]);
+    n_und = r.n_und;
+  }
+  void commit_lcr(int lcr_new, int lcr_events) {
+    lcr = lcr_new;
+    lcre = lcr_new - 1 >= 0 ? lcr_events : 0;
+  }
+
+  // the batch's one closing round trip (read in place from the pinned arena); a
+  // replay's order stays in HBM (lazy: counters, per-call counts and transaction sums only)
+  void close_batch(Batch& b) {
+    const bool lazy = b.got_order && lazy_order && !b.order_out;
+    const size_t off = d2h_pinned(s_out.p, 4 * (b.got_order && !lazy ? b.out.total() : b.out.header()));
+    const size_t off_tx = lazy ? d2h_pinned(s_out.p + b.out.o_tx, 4 * 2 * (size_t)b.out.ntxb) : 0;
     sync();
     const int32_t* ho = (const int32_t*)(pin + off);
-    const int32_t* htx = lazy ? (const int32_t*)(pin + off_tx) : ho + o_tx;
-    const int32_t nrecv = ho[0];
-    if (got_order) {
-      const int32_t* ids = ho + 8 + ncalls;
-      unsigned long long ntx = 0;
-      for (int b2 = 0; b2 < ntxb; b2++) {
-        unsigned long long v = 0;
-        memcpy(&v, htx + 2 * (size_t)b2, 8);
-        ntx += v;
-      }
+    const int32_t* htx = !b.got_order ? nullptr : lazy ? (const int32_t*)(pin + off_tx) : ho + b.out.o_tx;
+    const hge_plan::Results r = hge_plan::parse_results(b.out, ho, htx);
+    if (b.got_order) {
       if (lazy) {  // delivered into the pinned order buffer (sized at hge_replay_prepare)
-        if ((size_t)nrecv > pin_ord_cap) throw EngineError(HGE_ERR_INTERNAL, "order buffer below the ordered count");
+        if ((size_t)r.nrecv > pin_ord_cap) throw EngineError(HGE_ERR_INTERNAL, "order buffer below the ordered count");
         const int64_t td = now_ns();
-        if (!wrote_direct && nrecv) {
-          HIPCHK(hipMemcpyAsync(pin_ord, o_ids, 4 * (size_t)nrecv, hipMemcpyDeviceToHost, st));
+        if (!b.wrote_direct && r.nrecv) {
+          HIPCHK(hipMemcpyAsync(pin_ord, out_ids(b), 4 * (size_t)r.nrecv, hipMemcpyDeviceToHost, st));
           sync();
         }
         // the delivery's wall time after the sorts (hge_stage_times [5]; ~0 when written direct)
         stage_ms[5] = (float)((now_ns() - td) / 1e6);
-        cons_pin_n = nrecv;
-      } else {
-        consensus.insert(consensus.end(), ids, ids + nrecv);
+        cons_pin_n = r.nrecv;
       }
-      ctx += (int64_t)ntx;
-      if (order_out) order_out->insert(order_out->end(), ids, ids + nrecv);
-      if (counts_out)
-        for (int c = 0; c < ncalls; c++) counts_out->push_back(ho[8 + c]);
-      n_und = ho[1];
-    } else if (do_order && counts_out && !split_done) {
-      for (int c = 0; c < ncalls; c++) counts_out->push_back(0);
+      commit_order(r, b.ncalls, !lazy, b.order_out, b.counts_out);
+    } else if (b.do_order && b.counts_out && !b.split_done) {
+      for (int c = 0; c < b.ncalls; c++) b.counts_out->push_back(0);
     }
-    if (lcr_dev && ho[3] > lcr) {
-      lcr_up = true;
-      lcr_new = ho[3];
+    if (b.lcr_dev && r.lcr > lcr) {
+      b.lcr_up = true;
+      b.lcr_new = r.lcr;
     }
-    if (lcr_up) {
-      lcr = lcr_new;
-      lcre = lcr_new - 1 >= 0 ? ho[2] : 0;
-    }
-    tp[4] = now_ns();
-    if (tph)
-      fprintf(stderr, "[hge consensus] prologue %.3f ms, fame %.3f ms (incl. syncs), order enqueue %.3f ms, closing %.3f ms\n",
-              (tp[1] - tp[0]) / 1e6, (tp[2] - tp[1]) / 1e6, (tp[3] - tp[2]) / 1e6, (tp[4] - tp[3]) / 1e6);
-    prof_collect();
+    if (b.lcr_up) commit_lcr(b.lcr_new, r.lcr_events);
   }
 
   // split replay: the parts' fame decisions (each part's pairs [P0, P1)) all-gathered
@@ -2730,116 +2754,66 @@ struct hge_engine {
   // lanes per round in the group-scan kernels (a lane holds NW slots when N > 64)
   int group_lanes() const { return N <= 16 ? 16 : N <= 32 ? 32 : 64; }
 
-  // which 0: k_fame_decide (a split part: the pairs of its rounds, then the parts'
-  // decisions all-gathered) and the per-round timeline; which 1: persist
-  // decide_only: the pairs' decisions only (k_fame_call<.., false> takes the timeline)
-  void fame_dispatch(int which, const Tables& t, int nrounds, int npairs, int ncalls,
-                     const std::vector<int32_t>* pr_round = nullptr, const std::vector<int32_t>* pr_off = nullptr,
-                     bool decide_only = false) {
-    if (which == 1) {
-      KLAUNCH(k_fame_persist, dim3(div_up((int64_t)nrounds * N, 256)), dim3(256), 0, st, t, c_pr,
-              c_pr + nrounds, c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, s_clast.p,
-              s_dec.p);
-      return;
-    }
-    const int G = group_lanes();
+  // the windows' pairs [.., npairs) decided (k_fame_decide; a split part: the pairs of
+  // its rounds, then the parts' decisions all-gathered) and, with `timeline`, the
+  // per-round timeline (else k_fame_call<.., false> takes it)
+  void fame_decide(const Tables& t, const hge_plan::FameWindows& w, int npairs, bool timeline = true) {
+    const int nrounds = w.nrounds();
     int k_lo = 0, k_hi = nrounds;
-    if (split_on() && pr_round) split_rounds_of(sp.part, *pr_round, k_lo, k_hi);
-    const int p0 = k_lo < nrounds && pr_off ? (*pr_off)[k_lo] : (k_lo < nrounds ? 0 : npairs);
-    const int p1 = k_hi < nrounds && pr_off ? (*pr_off)[k_hi] : npairs;
-    const int items = (p1 - p0) * N;
-    if (items > 0) {
-      switch (NW) {
-#define DCASE(B)                                                                                     \
-  case B:                                                                                            \
-    if (N == 64 * B)                                                                                 \
-      KLAUNCH((k_fame_decide_blk<B>), dim3(p1 - p0), dim3(N), 0, st, t, c_pr + k_lo,                  \
-              c_pr + nrounds + k_lo, c_pr + 2 * nrounds + k_lo, k_hi - k_lo, p0, p1, c_nc, c_Rc,      \
-              s_dec.p, (const int32_t*)nullptr);                                                     \
-    else                                                                                             \
-      KLAUNCH((k_fame_decide<B>), dim3(div_up(items, 256)), dim3(256), 0, st, t, c_pr + k_lo,         \
-              c_pr + nrounds + k_lo, c_pr + 2 * nrounds + k_lo, k_hi - k_lo, p0, p1, c_nc, c_Rc,      \
-              s_dec.p);                                                                              \
-    break;
-        DCASE(1)
-        DCASE(2)
-        DCASE(3)
-        DCASE(4)
-#undef DCASE
-        default:
-          throw EngineError(HGE_ERR_INTERNAL, "unsupported N");
-      }
+    if (split_on()) split_rounds_of(sp.part, w.round, k_lo, k_hi);
+    const int p0 = k_lo < nrounds ? w.off[k_lo] : npairs;
+    const int p1 = k_hi < nrounds ? w.off[k_hi] : npairs;
+    if (p1 > p0 && N == 64 * NW) {
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3(p1 - p0), dim3(N), 0, st, t, c_pr + k_lo,
+                 c_pr + nrounds + k_lo, c_pr + 2 * nrounds + k_lo, k_hi - k_lo, p0, p1, c_nc, c_Rc, s_dec.p,
+                 (const int32_t*)nullptr);
+    } else if (p1 > p0) {
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide, dim3(div_up((p1 - p0) * N, 256)), dim3(256), 0, st, t, c_pr + k_lo,
+                 c_pr + nrounds + k_lo, c_pr + 2 * nrounds + k_lo, k_hi - k_lo, p0, p1, c_nc, c_Rc, s_dec.p);
     }
-    if (split_on() && pr_round) split_exchange_dec(*pr_round, *pr_off, npairs);
-    if (decide_only) return;
-    switch (NW) {
-#define FCASE(B)                                                                                 \
-  case B:                                                                                        \
-    if (G == 16)                                                                                 \
-      KLAUNCH((k_fame_timeline_g<16, 1>), dim3(div_up((int64_t)nrounds * 16, 256)), dim3(256), 0, \
-              st, t, c_pr, c_pr + nrounds, c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, c_nc, \
-              s_dec.p, s_decbit.p, c_Lc);                                                        \
-    else if (G == 32)                                                                            \
-      KLAUNCH((k_fame_timeline_g<32, 1>), dim3(div_up((int64_t)nrounds * 32, 256)), dim3(256), 0, \
-              st, t, c_pr, c_pr + nrounds, c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, c_nc, \
-              s_dec.p, s_decbit.p, c_Lc);                                                        \
-    else                                                                                         \
-      KLAUNCH((k_fame_timeline_g<64, B>), dim3(div_up((int64_t)nrounds * 64, 256)), dim3(256), 0, \
-              st, t, c_pr, c_pr + nrounds, c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, c_nc, \
-              s_dec.p, s_decbit.p, c_Lc);                                                        \
-    break;
-      FCASE(1)
-      FCASE(2)
-      FCASE(3)
-      FCASE(4)
-#undef FCASE
-      default:
-        throw EngineError(HGE_ERR_INTERNAL, "unsupported N");
+    if (split_on()) split_exchange_dec(w.round, w.off, npairs);
+    if (!timeline) return;
+    const int G = group_lanes();
+    const dim3 tgrid(div_up((int64_t)nrounds * G, 256));
+    const int32_t *pr_off = c_pr + nrounds, *pr_cf = c_pr + 2 * nrounds, *pr_len = c_pr + 3 * nrounds;
+    if (G == 16) {
+      KLAUNCH((k_fame_timeline_g<16, 1>), tgrid, dim3(256), 0, st, t, c_pr, pr_off, pr_cf, pr_len, nrounds, c_nc,
+              s_dec.p, s_decbit.p, c_Lc);
+    } else if (G == 32) {
+      KLAUNCH((k_fame_timeline_g<32, 1>), tgrid, dim3(256), 0, st, t, c_pr, pr_off, pr_cf, pr_len, nrounds, c_nc,
+              s_dec.p, s_decbit.p, c_Lc);
+    } else {
+      KLAUNCH_NW(NW, NW_PAT, k_fame_timeline_g, 64, tgrid, dim3(256), 0, st, t, c_pr, pr_off, pr_cf, pr_len,
+                 nrounds, c_nc, s_dec.p, s_decbit.p, c_Lc);
     }
-    (void)ncalls;
+  }
+  void fame_persist(const Tables& t, int nrounds) {
+    KLAUNCH(k_fame_persist, dim3(div_up((int64_t)nrounds * N, 256)), dim3(256), 0, st, t, c_pr, c_pr + nrounds,
+            c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, s_clast.p, s_dec.p);
   }
 
-  void recv_dispatch(const Tables& t, const int32_t* cand, int ncand, int ncalls, int rr_lo,
-                     int R_last, bool fresh, bool wla_done) {
-    // N > 16: the median is a wave-wide radix select (k_median_wave) over coalesced
-    // rows: the round frontier rows transposed (WLA, k_witness_la, for every round a
-    // candidate can receive) and the FD timestamp offsets (FDTD).  A fresh replay's
-    // candidate list is the identity (candidate q = event q).
+  // round received per candidate and its consensus timestamp.  N > 16: the median is a
+  // wave-wide radix select (k_median_wave) over coalesced rows: the round frontier rows
+  // transposed (WLA, ensure_wla, for every round a candidate can receive) and the FD
+  // timestamp offsets (FDTD).  A fresh replay's candidate list is the identity
+  // (candidate q = event q).
+  void recv_dispatch(Batch& b) {
     const bool wmed = N > 16;
-    const bool ident = fresh && cand == d_und.p && (int64_t)ncand == n_events;
+    const bool ident = b.fresh_und && b.cand == d_und.p && (int64_t)b.ncand == n_events;
     int32_t* bseg = nullptr;
     if (wmed) {
-      s_bseg.need(ncand);
+      s_bseg.need(b.ncand);
       bseg = s_bseg.p;
-      if (R_last > rr_lo && !wla_done) {
-        d_WLA.need((size_t)Rcap * N * N);
-        if (N > 64 && !wide32) d_WLR.need((size_t)Rcap * N * N);
-        Tables tw = tables();
-        KLAUNCH(k_witness_la, dim3(div_up(N, 64), div_up(N, 64), R_last - rr_lo), dim3(256), 0, st, tw,
-                rr_lo);
-      }
+      ensure_wla(b);
     }
-    switch (NW) {
-#define RCASE(B)                                                                                 \
-  case B:                                                                                        \
-    KLAUNCH(k_round_received<B>, dim3(div_up(ncand, 256)), dim3(256), 0, st, t, cand, \
-                       ncand, vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p, ncalls, 0, rr_lo, R_last, segoff_p, \
-                       s_segcnt.p,                                                               \
-                       s_segcall.p, s_segdec.p, s_segfws.p, s_theta.p, s_recv.p, s_rr.p,         \
-                       s_cts.p, bseg);                                                           \
-    if (wmed)                                                                                    \
-      KLAUNCH(k_median_wave<B>, dim3(div_up(ncand, 4 * MED_EPW)), dim3(256), 0, st, tables(),              \
-              ident ? (const int32_t*)nullptr : cand, ncand, s_recv.p, s_rr.p, bseg, s_segfws.p,  \
-              s_cts.p);                                                                          \
-    break;
-      RCASE(1)
-      RCASE(2)
-      RCASE(3)
-      RCASE(4)
-#undef RCASE
-      default:
-        throw EngineError(HGE_ERR_INTERNAL, "unsupported N");
-    }
+    const Tables t = tables();
+    KLAUNCH_NW(NW, NW_T, k_round_received, dim3(div_up(b.ncand, 256)), dim3(256), 0, st, t, b.cand, b.ncand,
+               vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p, b.ncalls, 0, b.rr_lo, b.R_last,
+               segoff_p, s_segcnt.p, s_segcall.p, s_segdec.p, s_segfws.p, s_theta.p, s_recv.p, s_rr.p, s_cts.p,
+               bseg);
+    if (wmed)
+      KLAUNCH_NW(NW, NW_T, k_median_wave, dim3(div_up(b.ncand, 4 * MED_EPW)), dim3(256), 0, st, t,
+                 ident ? (const int32_t*)nullptr : b.cand, b.ncand, s_recv.p, s_rr.p, bseg, s_segfws.p, s_cts.p);
   }
 
   // DivideRounds: everything inserted becomes visible to the consensus calls
@@ -2895,18 +2869,7 @@ struct hge_engine {
     cs_pending = false;
     Tables t = tables();
     und_appended = true;  // (n_divided == n0: the walk's block appends the new ids)
-    s_newwit.need(m);
-    RoundAssign ra{(int)n0, (int)n1, s_newwit.p, k_rs + 2, d_und.p + n_und};
-    int Gw = 1;
-    while (Gw < std::min(N, 64)) Gw <<= 1;
-    ra.minw = d_minw.p;
-    ra.G = Gw;
-    ra.und = d_und.p;
-    ra.n_und = (int)n_und;
-    ra.lo = (int)n_divided;
-    ra.hi = (int)n1;
-    ra.r_from = minw_full ? 0 : -1;
-    ra.rlo_dev = s_fst.p;
+    const RoundAssign ra = round_assign(n0, n1, true);
     const int64_t guess = m + 16 * (int64_t)N;
     KLAUNCH(k_fss<16>, dim3((unsigned)std::min<int64_t>(1024, div_up(guess * 16, 256))), dim3(256), 0, st, t, k_lo,
             k_lo + N, 0, (int32_t*)nullptr, (uint16_t*)d_FSS.p, (const int32_t*)(k_lo + 2 * N));
@@ -2922,17 +2885,16 @@ struct hge_engine {
     // ---- consensus of the one call, control built on the device
     const int Rmax = R + (int)m + 1;
     const int nround_max = std::max(1, Rmax - 2 - lcr), nr_max = std::max(1, Rmax);
-    const int ncand = (int)n_und;
-    const size_t o_Rc = 2, o_Lc = 3, o_fl = 4, o_pr = 8, o_pidx = o_pr + 4 * (size_t)nround_max;
-    const size_t o_sgo = o_pidx + nr_max;
-    s_cctl.need(o_sgo + nr_max + 1);
-    c_nc = (int64_t*)s_cctl.p;
-    c_Rc = s_cctl.p + o_Rc;
-    c_Lc = s_cctl.p + o_Lc;
-    c_flags = s_cctl.p + o_fl;
-    c_pr = s_cctl.p + o_pr;
-    c_pidx = s_cctl.p + o_pidx;
-    c_sgo = s_cctl.p + o_sgo;
+    Batch b;
+    b.calls = &n_divided;
+    b.ncalls = 1;
+    b.do_fame = b.do_order = b.commit = b.ord = true;
+    b.cand = d_und.p;
+    b.ncand = (int)n_und;
+    b.out = hge_plan::results_layout(1, b.ncand);
+    b.ctl = hge_plan::ctl_layout(1, nround_max, nr_max);
+    s_cctl.need(b.ctl.total);
+    bind_ctl(b.ctl);
     s_dec.need((size_t)nround_max * N);
     s_decbit.need(nround_max);
     s_LCR.need(1);
@@ -2944,22 +2906,10 @@ struct hge_engine {
     s_segdec.need(nslot);
     s_segfws.need(nslot * NW);
     s_theta.need(nslot * N);
-    const size_t o_tx = (8 + 1 + (size_t)ncand + 1) & ~(size_t)1;
-    const int ntxb = div_up(ncand, 256);
-    s_out.need(o_tx + 2 * (size_t)ntxb);
-    s_recv.need(ncand);
-    s_rr.need(ncand);
-    s_cts.need(ncand);
-    s_fund.need(ncand);
-    s_upos.need(ncand);
-    s_bpos.need(4);
-    s_und2.need(d_und.n);
-    s_keys.need((size_t)ncand * sizeof(OKey));
-    s_keys2.need((size_t)ncand * sizeof(OKey));
-    t = tables();
+    s_out.need(b.out.total());
     DynCall dc{};
     dc.lcr = lcr;
-    dc.ncand = ncand;
+    dc.ncand = b.ncand;
     dc.Rcap = Rcap;
     dc.n_c = n_divided;
     dc.rstate = k_rs;
@@ -2976,42 +2926,12 @@ struct hge_engine {
     dc.LCR = s_LCR.p;
     dc.clast = s_clast.p;
     dc.out = s_out.p;
-    OrderCall& o = dc.o;
-    o.segcnt = s_segcnt.p;
-    o.seg_call = s_segcall.p;
-    o.seg_round = s_seground.p;
-    o.seg_dec = s_segdec.p;
-    o.seg_fws = s_segfws.p;
-    o.theta = s_theta.p;
-    o.cand = d_und.p;
-    o.ncand = ncand;
-    o.recv = s_recv.p;
-    o.rr = s_rr.p;
-    o.cts = s_cts.p;
-    o.cnt = s_out.p + 8;
-    o.bpos = s_bpos.p;
-    o.total = s_out.p;
-    o.blist = s_bpos.p + 1;
-    o.nblist = s_bpos.p + 2;
-    o.f_und = s_fund.p;
-    o.upos = s_upos.p;
-    o.nund = s_out.p + 1;
-    o.und_out = s_und2.p;
-    o.k1 = (OKey*)s_keys.p;
-    o.k2 = (OKey*)s_keys2.p;
-    o.ev_rr = d_rr.p;
-    o.ev_cts = d_cts.p;
-    o.ntx = (unsigned long long*)(s_out.p + o_tx);
-    o.ntxb = ntxb;
-    o.ids = s_out.p + 9;
-    o.lcr_old = lcr;
-    o.n_lo = (int)n_divided;
-    o.n1 = (int)n_divided;
-    o.lcre_out = s_out.p + 2;
+    dc.o = order_call(b, 1);  // (the buffers; the kernel sets the rounds, the windows and front)
+    t = tables();
     KLAUNCH(k_consensus_dyn<16>, dim3(1), dim3(1024), 0, st, t, dc);
     std::swap(d_und, s_und2);
     // ---- the one round trip: the results block and the rounds' first witnesses
-    const size_t off = d2h_pinned(s_out.p, 4 * (o_tx + 2 * (size_t)ntxb));
+    const size_t off = d2h_pinned(s_out.p, 4 * b.out.total());
     const size_t offw = d2h_pinned(d_minw.p, 4 * ((size_t)Rcap + 4));
     sync();
     const int32_t* hw = (const int32_t*)(pin + offw);
@@ -3025,22 +2945,9 @@ struct hge_engine {
     mnr_key[0] = -1;
     update_rdiv();
     const int32_t* ho = (const int32_t*)(pin + off);
-    const int32_t nrecv = ho[0];
-    const int32_t* ids = ho + 9;
-    unsigned long long ntx = 0;
-    for (int b2 = 0; b2 < ntxb; b2++) {
-      unsigned long long v = 0;
-      memcpy(&v, ho + o_tx + 2 * (size_t)b2, 8);
-      ntx += v;
-    }
-    consensus.insert(consensus.end(), ids, ids + nrecv);
-    order.insert(order.end(), ids, ids + nrecv);
-    ctx += (int64_t)ntx;
-    n_und = ho[1];
-    if (ho[3] > lcr) {
-      lcr = ho[3];
-      lcre = lcr - 1 >= 0 ? ho[2] : 0;
-    }
+    const hge_plan::Results r = hge_plan::parse_results(b.out, ho, ho + b.out.o_tx);
+    commit_order(r, 1, true, &order, nullptr);
+    if (r.lcr > lcr) commit_lcr(r.lcr, r.lcr_events);
     prof_collect();
     return true;
   }

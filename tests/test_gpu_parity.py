@@ -59,7 +59,11 @@ def test_random_gossip(engines, n, events, k):
 
 @pytest.mark.parametrize("n,events,k", [(32, 4000, 32), (64, 4000, 64),
                                          # N = 192: DecideFame's per-round widening (N % 64 == 0, N >= 192)
-                                         # and uint16 FD rows; N = 200 / 224: the median's 4-witness
+                                         # and uint16 FD rows.  This stream does take a widening pass
+                                         # (k_dec_relayout, then k_fame_decide_blk over the new pairs): by
+                                         # the oracle's per-call Rounds() and LastConsensusRound, round 4 is
+                                         # decided at call 92 with R_c = 8 > 4 + 3, past its first window.
+                                         # N = 200 / 224: the median's 4-witness
                                          # lanes past N / 4 (N < 256) and uint16 FD rows
                                          (192, 24000, 192), (200, 16000, 200), (224, 16000, 224)])
 def test_random_gossip_wide(engines, n, events, k):
