@@ -21,6 +21,7 @@
 #include <optional>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/hge.h"
@@ -45,16 +46,18 @@ using namespace hge;
 
 // every launch is checked: a launch the runtime refuses (e.g. too much LDS)
 // must fail the call, never leave a table silently unwritten
-#define KLAUNCH(kern, ...)                                                             \
+// KLAUNCH_AS: a kernel pointer chosen at run time (WalkKernels) under its instantiation's name
+#define KLAUNCH_AS(name, kern, ...)                                                    \
   do {                                                                                 \
     hp.launches++;                                                                     \
-    prof_begin(#kern);                                                                 \
+    prof_begin(name);                                                                  \
     hipLaunchKernelGGL(kern, __VA_ARGS__);                                             \
     const hipError_t le_ = hipGetLastError();                                          \
     if (le_ != hipSuccess)                                                             \
-      throw EngineError(HGE_ERR_DEVICE, std::string("launch " #kern ": ") + hipGetErrorString(le_)); \
+      throw EngineError(HGE_ERR_DEVICE, std::string("launch ") + name + ": " + hipGetErrorString(le_)); \
     prof_end();                                                                        \
   } while (0)
+#define KLAUNCH(kern, ...) KLAUNCH_AS(#kern, kern, __VA_ARGS__)
 
 // Run-time NW (1..4) -> template argument, the one place that does it:
 //   KLAUNCH_NW(NW, SHAPE, kernel, [template arguments around the width,] launch arguments...)
@@ -233,11 +236,7 @@ struct hge_engine {
   DBuf<unsigned char> s_keys, s_keys2;
   DBuf<int32_t> s_part, s_fst, s_relay, s_rfail;
   DBuf<uint8_t> s_dec2;  // selective fame widening: the new layout's decisions
-  bool fst_fused = false;  // this batch's k_la_seq ran k_frontier_start's block
-  bool fd_direct = false;  // this batch's k_la_seq wrote the FD rows (N <= 16)
-  bool asg_fused = false;  // this attempt's rounds walk assigned the new events' rounds
-  bool tail_fused = false;  // ... and did k_round_tail's work
-  bool minw_full = true;    // d_minw's rows are stale: the next rounds tail recomputes all
+  bool minw_full = true;   // d_minw's rows are stale: the next rounds tail recomputes all
   // coordinate sweeps: transposed tables and scratch
   int n_sweeps = 0;
   DBuf<int32_t> d_FDT, s_chg, s_bar, s_dirty;
@@ -288,16 +287,10 @@ struct hge_engine {
   int32_t *c_Rc = nullptr, *c_Lc = nullptr, *c_flags = nullptr, *c_pr = nullptr, *c_pidx = nullptr;
   int32_t* c_sgo = nullptr;
   const int32_t* segoff_p = nullptr;  // segment offsets used by k_round_received
-  // coordinates control block (coords): pointers into s_kctl
+  // the coordinate step's control block (hge_plan::CoordsCtl, bound in CoordStep) and its host staging
   DBuf<int32_t> s_kctl;
   std::vector<int32_t> h_kctl;
-  std::vector<int2> h_segs;
-  bool qlo_fused = false;  // k_fd_qlo ran with k_chain_fill (coords_a)
-  int32_t *k_rs = nullptr, *k_len = nullptr, *k_plo = nullptr, *k_qlo = nullptr, *k_lo = nullptr;
-  int2* k_segs = nullptr;
-  int32_t* k_segbase = nullptr;
-  int32_t* k_fd = nullptr;  // split: the candidates' chain positions [lo N, hi N)
-  int32_t* k_risky1 = nullptr;  // la_windows_run's one-window risky id (-1 as uploaded)
+  std::vector<hge_plan::Seg> h_segs;
   bool und_fresh = false;  // the candidate list is every event of a fresh replay
   float stage_ms[7] = {};
 
@@ -897,10 +890,51 @@ struct hge_engine {
   }
 
   // ---------------- coordinates + rounds for [n_coords, n_events) ----------------
-  // coordinates + rounds for [n_coords, n_events): coords_a (sweeps and
-  // transposes) then coords_b (the rounds frontier and what follows).  The
-  // cross-GPU split (hge_split_*) runs a walker between the two.
-  bool cs_pending = false, cs_fresh = false;
+  // coords_a (the control block, lastAncestors, firstDescendants) then coords_b (the
+  // rounds frontier and what follows).  What their stages share is a CoordStep: coords_a
+  // makes it, coords_b (or online_fast) takes it, and in between the step is pending
+  // (cstep has a value): the cross-GPU split (hge_split_*) runs a walker there.
+  struct CoordStep {
+    bool fresh = false;      // nothing had coordinates or rounds before
+    int64_t n0 = 0, n1 = 0;  // the new ids
+    int maxnew = 0;          // most new positions on one chain, + 1
+    int tot0 = 0;            // a fresh walk's fss rows (every chain's length)
+    int SEG = 0, nseg = 0;   // the sweeps' segment length and count
+    int maxlen = 0, minlen = 0;  // the longest and the shortest chain
+    enum class La { Windows, Seq, Sweeps } la = La::Sweeps;  // how lastAncestors are computed
+    // the control block's regions in s_kctl (bind_kctl)
+    int32_t *rstate = nullptr, *olen = nullptr, *len = nullptr, *plo = nullptr, *qlo = nullptr;
+    int32_t *fss_lo = nullptr, *fss_off = nullptr, *fss_total = nullptr, *segbase = nullptr;
+    const int2* segs = nullptr;
+    int32_t *cand_lo = nullptr, *cand_hi = nullptr;  // a split part's candidates (else null)
+    int32_t* risky1 = nullptr;  // the one-window lastAncestors pass's risky id (-1 as uploaded)
+    const UpEv* up = nullptr;   // the chain-table fill's source: the packed upload, or null (the tables)
+    UpDst up_dst{};
+    // what earlier kernels of the step did already
+    bool frontier_started = false;  // k_frontier_start's block (k_chain_fill_qlo, k_la_seq)
+    bool qlo_done = false;          // k_fd_qlo's blocks (the same two)
+    bool fd_done = false;           // the FD rows and FDT runs (k_la_seq, N <= 16)
+    bool take_frontier_start() { return std::exchange(frontier_started, false); }  // (a later attempt starts again)
+  };
+  std::optional<CoordStep> cstep;
+  // what one attempt's rounds walk did besides walking
+  struct Walk {
+    bool assigned = false;   // the new events' rounds (k_round_assign's work)
+    bool tail_done = false;  // ... and k_round_tail's work
+    const int32_t* err_src = nullptr;  // a wide walk's hand-off error flag (it comes back with the rounds tail)
+    bool host_err = false;             // ... or the host saw the error already
+  };
+  void bind_kctl(CoordStep& s, const hge_plan::CoordsCtl& L) const {
+    int32_t* p = s_kctl.p;
+    s.rstate = p + L.rstate, s.olen = p + L.olen(), s.len = p + L.nlen();
+    s.plo = p + L.plo, s.qlo = p + L.qlo;
+    s.fss_lo = p + L.fss_lo(), s.fss_off = p + L.fss_off(), s.fss_total = p + L.fss_total();
+    s.segs = (const int2*)(p + L.segs), s.segbase = p + L.segbase;
+    s.cand_lo = split_on() ? p + L.cand_lo() : nullptr;
+    s.cand_hi = split_on() ? p + L.cand_hi() : nullptr;
+    s.risky1 = p + L.risky;
+    s.up = L.up_words ? (const UpEv*)(p + L.up) : nullptr;
+  }
   std::chrono::steady_clock::time_point w_start;
   // cross-GPU split: the joined frontier rows of the walkers (hge_split_finish)
   bool ext_on = false, ext_natural = false;
@@ -958,9 +992,9 @@ struct hge_engine {
     if (emulating()) return;  // the caller fills the other parts' slots from the record
     if (x_fn(x_ctx, 1, bytes, &b) != 0) throw EngineError(HGE_ERR_DEVICE, "split exchange failed");
   }
-  // fame rounds of part g: the pr_* indices [k_lo, k_hi) whose round's first witness
+  // fame rounds of part g: the pr_* indices [win_lo, win_hi) whose round's first witness
   // lies in the part's events (h_minw is ascending in the round)
-  void split_rounds_of(int g, const std::vector<int32_t>& pr_round, int& k_lo, int& k_hi) const {
+  void split_rounds_of(int g, const std::vector<int32_t>& pr_round, int& win_lo, int& win_hi) const {
     const int nr = (int)pr_round.size();
     auto first_at = [&](int64_t ev) {
       int lo = 0, hi = nr;
@@ -971,375 +1005,348 @@ struct hge_engine {
       }
       return lo;
     };
-    k_lo = g == 0 ? 0 : first_at(sp.a[g]);
-    k_hi = g == sp.nparts - 1 ? nr : first_at(sp.a[g + 1]);
+    win_lo = g == 0 ? 0 : first_at(sp.a[g]);
+    win_hi = g == sp.nparts - 1 ? nr : first_at(sp.a[g + 1]);
   }
-  int64_t cs_n0 = 0, cs_n1 = 0;
   // the candidates' lowest round, read back with the round count (coords_b) for the
   // undetermined list of n_und = key[0] + key[2] - key[1] events after the divide
   // that raises n_divided from key[1] to key[2] (key[0] < 0: none)
   int32_t mnr_pre = 0;
   int64_t mnr_key[3] = {-1, 0, 0};
-  int cs_tot0 = 0;
   void coords() {
-    if (!coords_a()) return;
-    coords_b();
+    if (coords_a()) coords_b();
   }
+  // the wide kernels' tile width; the lanes per witness of the bitset kernels
+  int npow() const { return N <= 64 ? 64 : N <= 128 ? 128 : 256; }
+  int wit_group() const {
+    int G = 1;
+    while (G < std::min(N, 64)) G <<= 1;
+    return G;
+  }
+
+  // the step's first half; leaves it pending (cstep); false: no new event
   bool coords_a() {
-    fst_fused = false;
+    cstep.reset();
     upload();
     if (wide32_pending) to_wide32();
-    const int64_t n0 = n_coords, n1 = n_events;
-    if (n1 == n0) return false;
-    Tables t = tables();
-    // control block (one upload): round state, chain lengths, transpose bounds,
-    // fss offsets of a fresh walk and the sweep segments
+    if (n_events == n_coords) return false;
+    CoordStep s;
+    plan_step(s);
+    const Tables t = tables();
+    chain_fill(t, s);
+    last_ancestors(t, s);
+    first_descendants(t, s);
+    cstep = s;
+    return true;
+  }
+  // the control block (hge_plan::CoordsCtl), one upload
+  void plan_step(CoordStep& s) {
+    s.n0 = n_coords;
+    s.n1 = n_events;
     // segment length: latency-bound sweeps (small N) like short segments, bandwidth-bound
     // ones (large N) long ones (fewer stale carries)
-    const int SEG = N <= 32 ? 16 : 64;
-    std::vector<int2>& segs = h_segs;
-    segs.clear();
-    // only the fixed-point sweeps read the segment list (the windowed pass and the
-    // one-pass batch kernel do not): 156k segments and their sort were ~3 ms of host
-    // time at the start of a 256/10M replay
-    const bool sweeps = !(sweep16() && la_windows()) && !la_seq_ok(n1 - n0);
-    int maxnew = 0;
+    s.SEG = N <= 32 ? 16 : 64;
+    // only the fixed-point sweeps read the segment list: 156k segments and their sort
+    // were ~3 ms of host time at the start of a 256/10M replay
+    s.la = sweep16() && la_windows() ? CoordStep::La::Windows
+           : la_seq_ok(s.n1 - s.n0)  ? CoordStep::La::Seq
+                                     : CoordStep::La::Sweeps;
+    const bool sweeps = s.la == CoordStep::La::Sweeps;
+    h_segs.clear();
+    if (sweeps) hge_plan::sweep_segments(h_segs, coords_len, chain_len, s.SEG);
+    s.nseg = sweeps ? (int)h_segs.size() : 1;
+    s.fresh = R == 0;
+    s.minlen = INT32_MAX;
     for (int c = 0; c < N; c++) {
-      maxnew = std::max(maxnew, chain_len[c] - coords_len[c] + 1);
-      if (sweeps)
-        for (int k = coords_len[c]; k < chain_len[c]; k += SEG) segs.push_back(make_int2(c, k));
+      s.maxnew = std::max(s.maxnew, chain_len[c] - coords_len[c] + 1);
+      s.fresh = s.fresh && coords_len[c] == 0;
+      s.maxlen = std::max(s.maxlen, chain_len[c]);
+      s.minlen = std::min(s.minlen, chain_len[c]);
     }
-    // position-major order: workgroups are dispatched roughly in index order, so
-    // early positions of every chain are swept first and later segments read
-    // rows already updated in this sweep (Gauss-Seidel in time order)
-    if (sweeps)
-      std::stable_sort(segs.begin(), segs.end(), [](const int2& a, const int2& b) { return a.y < b.y; });
-    bool fresh = R == 0;
-    for (int c = 0; c < N; c++) fresh = fresh && coords_len[c] == 0;
-    const size_t o_len = 4, o_plo = o_len + 2 * N, o_qlo = o_plo + N, o_lo = o_qlo + N;
-    const size_t o_seg = (o_lo + 2 * N + 1 + 1) & ~(size_t)1;
-    const size_t o_sb = o_seg + 2 * segs.size();  // chain-major segment bases (sweep skipping)
-    const size_t o_fd = o_sb + N;  // split: the chain positions of the part's candidates
-    std::vector<int32_t>& kc = h_kctl;
-    kc.assign(o_fd + 2 * N + 1, 0);
-    kc[o_fd + 2 * N] = -1;  // the one-window lastAncestors pass's risky id (la_windows_run)
+    std::vector<int32_t> cand;
     if (split_on()) {
       // FD timestamp rows (the median's input) of the ids [cand_lo, the part's end)
       const int64_t A = sp.clo[sp.part], B = sp.a[sp.part + 1];
+      cand.resize(2 * (size_t)N);
       for (int c = 0; c < N; c++) {
         const std::vector<int32_t>& ch = h_chain[c];
-        kc[o_fd + c] = (int)(std::lower_bound(ch.begin(), ch.end(), (int32_t)A) - ch.begin());
-        kc[o_fd + N + c] = (int)(std::lower_bound(ch.begin(), ch.end(), (int32_t)B) - ch.begin());
+        cand[c] = (int)(std::lower_bound(ch.begin(), ch.end(), (int32_t)A) - ch.begin());
+        cand[N + c] = (int)(std::lower_bound(ch.begin(), ch.end(), (int32_t)B) - ch.begin());
       }
     }
-    kc[0] = R;  // rstate: {R, overflow}, new-witness count
-    int tot0 = 0;
-    for (int c = 0; c < N; c++) {
-      kc[o_len + c] = coords_len[c];
-      kc[o_len + N + c] = chain_len[c];
-      kc[o_plo + c] = std::max(coords_len[c] - 1, 0);
-      kc[o_lo + N + c] = tot0;  // fresh walk: fss rows from position 0 (qlo = 0 too)
-      tot0 += chain_len[c];
-    }
-    for (int c = 0, b = 0; c < N; c++) {
-      kc[o_sb + c] = b;
-      b += div_up(chain_len[c] - coords_len[c], SEG);
-    }
-    kc[o_lo + 2 * N] = tot0;
-    if (!segs.empty()) memcpy(&kc[o_seg], segs.data(), sizeof(int2) * segs.size());
     // the packed event records (an online call's upload) ride in the same copy
-    const bool packed = up_n0 == n0 && up_n1 == n1;
-    const size_t o_up = (kc.size() + 3) & ~(size_t)3;  // 16-byte aligned
-    const size_t up_words = packed ? (sizeof(UpEv) * h_up.size() + 3) / 4 : 0;
-    if (packed) {
-      static_assert(sizeof(UpEv) % 4 == 0, "records are whole words");
-      kc.resize(o_up + up_words, 0);
-      memcpy(&kc[o_up], h_up.data(), sizeof(UpEv) * h_up.size());
-    }
-    s_kctl.need(kc.size());
-    h2d(s_kctl.p, kc.data(), 4 * kc.size());
-    k_rs = s_kctl.p;
-    k_len = s_kctl.p + o_len;
-    k_plo = s_kctl.p + o_plo;
-    k_qlo = s_kctl.p + o_qlo;
-    k_lo = s_kctl.p + o_lo;
-    k_segs = (int2*)(s_kctl.p + o_seg);
-    k_segbase = s_kctl.p + o_sb;
-    k_fd = split_on() ? s_kctl.p + o_fd : nullptr;
-    k_risky1 = s_kctl.p + o_fd + 2 * N;
-    {
-      fill_up = packed ? (const UpEv*)(s_kctl.p + o_up) : (const UpEv*)nullptr;
-      fill_dst = UpDst{d_creator.p, d_index.p, d_sp.p, d_op.p, d_ntx.p, d_ts.p, d_S.p, d_coin.p};
-      up_n0 = up_n1 = -1;
-      h_up.clear();
-      qlo_fused = false;
-      if (!la_seq_ok(n1 - n0)) {  // (k_la_seq fills the chain table itself)
-        const int nfb = div_up((int)(n1 - n0), 256);
-        if (!fresh && N <= 256) {  // + k_fd_qlo's blocks (coords_b)
-          // + k_frontier_start's block for the wide rounds walk (rounds_coop)
-          fst_fused = N > 32 && !wide32 && !frontier_fallback && !split_on() && !ext_on;
-          if (fst_fused) {
-            s_fst.need(N + 1);
-            s_bar.need(2);
-            s_gran.need(2 * (size_t)N);
-          }
-          KLAUNCH(k_chain_fill_qlo, dim3(nfb + N + (fst_fused ? 1 : 0)), dim3(256), 0, st, t, (int)n0, (int)n1,
-                  fill_up, fill_dst, nfb, (const int32_t*)k_len, (const int32_t*)(k_len + N), k_qlo,
-                  fst_fused ? s_fst.p : (int32_t*)nullptr, fst_fused ? s_bar.p : (int32_t*)nullptr,
-                  fst_fused ? (uint64_t*)s_gran.p : (uint64_t*)nullptr, 2 * N);
-          qlo_fused = true;
-        } else {
-          KLAUNCH(k_chain_fill, dim3(nfb), dim3(256), 0, st, t, (int)n0, (int)n1, fill_up, fill_dst);
-        }
+    const bool packed = up_n0 == s.n0 && up_n1 == s.n1;
+    if (packed && h_up.empty()) throw EngineError(HGE_ERR_INTERNAL, "packed upload without records");
+    static_assert(sizeof(UpEv) % 4 == 0, "records are whole words");
+    static_assert(sizeof(hge_plan::Seg) == sizeof(int2), "the kernels read segments as int2");
+    const hge_plan::CoordsCtl L =
+        hge_plan::coords_ctl_layout(N, h_segs.size(), packed ? sizeof(UpEv) * h_up.size() / 4 : 0);
+    s.tot0 = hge_plan::fill_coords_ctl(h_kctl, L, R, coords_len, chain_len, h_segs, s.SEG, cand);
+    if (packed) memcpy(&h_kctl[L.up], h_up.data(), sizeof(UpEv) * h_up.size());
+    s_kctl.need(h_kctl.size());
+    h2d(s_kctl.p, h_kctl.data(), 4 * h_kctl.size());
+    bind_kctl(s, L);
+    s.up_dst = UpDst{d_creator.p, d_index.p, d_sp.p, d_op.p, d_ntx.p, d_ts.p, d_S.p, d_coin.p};
+    up_n0 = up_n1 = -1;
+    h_up.clear();
+  }
+  // the chain table for the new ids, unless k_la_seq will fill it; past a fresh state
+  // with k_fd_qlo's blocks and, for the wide rounds walk, k_frontier_start's
+  void chain_fill(const Tables& t, CoordStep& s) {
+    if (s.la == CoordStep::La::Seq) return;
+    const int nfb = div_up((int)(s.n1 - s.n0), 256);
+    if (!s.fresh && N <= 256) {
+      const bool fst = N > 32 && !wide32 && !frontier_fallback && !split_on() && !ext_on;
+      if (fst) {
+        s_fst.need(N + 1);
+        s_bar.need(2);
+        s_gran.need(2 * (size_t)N);
       }
+      KLAUNCH(k_chain_fill_qlo, dim3(nfb + N + (fst ? 1 : 0)), dim3(256), 0, st, t, (int)s.n0, (int)s.n1,
+              s.up, s.up_dst, nfb, (const int32_t*)s.olen, (const int32_t*)s.len, s.qlo,
+              fst ? s_fst.p : (int32_t*)nullptr, fst ? s_bar.p : (int32_t*)nullptr,
+              fst ? (uint64_t*)s_gran.p : (uint64_t*)nullptr, 2 * N);
+      s.frontier_started = fst;
+      s.qlo_done = true;
+    } else {
+      KLAUNCH(k_chain_fill, dim3(nfb), dim3(256), 0, st, t, (int)s.n0, (int)s.n1, s.up, s.up_dst);
     }
-    coords_sweep(t, sweeps ? (int)segs.size() : 1, SEG, maxnew, fresh);
-    cs_pending = true;
-    cs_fresh = fresh;
-    cs_n0 = n0;
-    cs_n1 = n1;
-    cs_tot0 = tot0;
-    return true;
   }
   // what a single-block rounds walk does after walking: the rounds of the new events
   // [n0, n1) (k_round_assign's work; und_appended: their ids appended to the
   // undetermined list) and, with `tail`, k_round_tail's work
-  RoundAssign round_assign(int64_t n0, int64_t n1, bool tail) {
-    s_newwit.need(n1 - n0);
-    RoundAssign ra{(int)n0, (int)n1, s_newwit.p, k_rs + 2, und_appended ? d_und.p + n_und : (int32_t*)nullptr};
+  RoundAssign round_assign(const CoordStep& s, bool tail) {
+    s_newwit.need(s.n1 - s.n0);
+    RoundAssign ra{(int)s.n0, (int)s.n1, s_newwit.p, s.rstate + 2, und_appended ? d_und.p + n_und : (int32_t*)nullptr};
     if (tail) {
-      int Gw = 1;
-      while (Gw < std::min(N, 64)) Gw <<= 1;
       ra.minw = d_minw.p;
-      ra.G = Gw;
+      ra.G = wit_group();
       ra.und = d_und.p;
       ra.n_und = (int)n_und;
       ra.lo = (int)n_divided;
-      ra.hi = (int)n1;
+      ra.hi = (int)s.n1;
       ra.r_from = minw_full ? 0 : -1;
       ra.rlo_dev = s_fst.p;
     }
     return ra;
   }
+  // The step's second half: the rounds walk, the new events' rounds, the rounds tail,
+  // then ONE round trip for the round count and minw.  The kernels stand down if the
+  // rounds table overflowed or a wide walk's hand-off timed out: the loop mends that
+  // and walks again.
+  enum class RoundsOutcome { Done, Grow, HandoffTimeout };
   void coords_b() {
-    cs_pending = false;
-    const bool fresh = cs_fresh;
-    const int64_t n0 = cs_n0, n1 = cs_n1;
-    const int tot0 = cs_tot0;
-    const int m = (int)(n1 - n0);
-    Tables t = tables();
-    // rounds frontier
+    CoordStep s = *cstep;
+    cstep.reset();
     for (bool retry = false;; retry = true) {
-      // the wide frontier grids stay on the device until the sync below: two such
+      // the wide frontier grids stay on the device until the readback's sync: two such
       // grids on one device must not overlap (frontier_lock)
       std::unique_lock<std::mutex> flk;
       if (N > 32) flk = frontier_lock();
-      int32_t rs[3] = {R, 0, 0};
-      if (retry) h2d(k_rs, rs, 12);
-      asg_fused = false;
-      tail_fused = false;
-      t = tables();
-      const int NP = (N + 15) & ~15;
-      if (N > 32 && (wide32 || frontier_fallback)) {
-        rounds_step32();
-      } else if (N > 32) {
-        rounds_coop(fresh);
-      } else {
-        // first-strong-seer rows for every event that can still be a frontier member
-        // (from a fresh state the frontier starts at round 0, position 0: no round trip)
-        int maxlen = 0;
-        for (int c = 0; c < N; c++) maxlen = std::max(maxlen, chain_len[c]);
-        const int Rprev = R;  // C rows >= Rprev are empty before this batch
-        if (!fresh && maxlen < 0xFFFF) {
-          // an online call: the walk's first round, its k_fss rows and their count
-          // stay on the device (k_frontier_start writes them; k_fss loops over the
-          // count, k_rounds_walk stands down at INF32): no host round trip
-          s_fst.need(N + 1);
-          if (!fst_fused || retry)  // (else k_la_seq's last block wrote them)
-            KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, k_len, k_len + N, s_fst.p, k_lo,
-                    (int32_t*)nullptr, (uint64_t*)nullptr, 0);
-          const int64_t guess = m + 16 * (int64_t)N;  // the grid loops past it
-          // the walk's block also assigns the new events' rounds (k_round_assign's work)
-          und_appended = dividing && n_divided == n0;
-          // ... and k_round_tail's work (the new witnesses' bitsets, the first witness
-          // of the rounds from the walk's first one, the candidates' lowest round)
-          tail_fused = n_und + (n1 - n_divided) <= 65536;
-          const RoundAssign ra = round_assign(n0, n1, tail_fused);
-          asg_fused = true;
-#define FSSD(NPC, LPC, B)                                                                              \
-  KLAUNCH(k_fss<NPC>, dim3((unsigned)std::min<int64_t>(1024, div_up(guess * NPC, 256))), dim3(256), 0, st, t, \
-          k_lo, k_lo + N, 0, (int32_t*)nullptr, (uint16_t*)d_FSS.p, (const int32_t*)(k_lo + 2 * N));          \
-  KLAUNCH((k_rounds_walk<NPC, LPC, B>), dim3(1), dim3(1024), 0, st, t, (const uint16_t*)d_FSS.p, k_len,       \
-          k_len + N, k_rs, 0, Rprev, dbg_p(), (const int32_t*)s_fst.p, ra);
-          if (NP == 16) {
-            FSSD(16, 4, 256)
-          } else {
-            FSSD(32, 2, 64)
-          }
-#undef FSSD
-        } else {
-        std::vector<int32_t> fst(N + 1, 0);
-        if (!fresh) {
-          s_fst.need(N + 1);
-          KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, k_len, k_len + N, s_fst.p, (int32_t*)nullptr,
-                  (int32_t*)nullptr, (uint64_t*)nullptr, 0);
-          readback(fst.data(), s_fst.p, N + 1);
-        }
-        const int rlo = fst[0];
-        if (rlo != INF32) {
-          int tot = fresh ? tot0 : 0;
-          if (!fresh) {
-            std::vector<int32_t> lo_off(2 * N + 1);
-            for (int c = 0; c < N; c++) {
-              lo_off[c] = fst[1 + c];
-              lo_off[N + c] = tot;
-              tot += std::max(0, chain_len[c] - fst[1 + c]);
-            }
-            lo_off[2 * N] = tot;
-            h2d(k_lo, lo_off.data(), 4 * (2 * N + 1));
-          }
-          if (tot > 0) {
-            // the LDS walk keeps chain positions as uint16; longer chains take the
-            // register walk over the global fss rows
-#define FSSL(NPC, LPC, B)                                                                          \
-  if (maxlen < 0xFFFF) {                                                                           \
-    KLAUNCH(k_fss<NPC>, dim3(div_up((int64_t)tot * NPC, 256)), dim3(256), 0, st, t, k_lo, k_lo + N, \
-            tot, (int32_t*)nullptr, (uint16_t*)d_FSS.p, (const int32_t*)nullptr);                  \
-    const int nw = fresh ? spec_walkers(maxlen) : 0;                                               \
-    if (nw > 1) {                                                                                  \
-      const char* hc = getenv("HGE_WALK_HCAP"); /* tests: force the capacity fallback */          \
-      const int Hcap = hc ? std::max(2, atoi(hc))                                                  \
-                          : std::max(256, std::min(Rcap, 3 * (Rcap / nw) + 256));                  \
-      if ((size_t)nw * Hcap * N > s_H.n) {                                                         \
-        s_H.need((size_t)nw * Hcap * N); /* epoch 0 never matches a launch's tag */                \
-        HIPCHK(hipMemsetAsync(s_H.p, 0, s_H.n * sizeof(uint64_t), st));                            \
-      }                                                                                            \
-      s_hres.need(4 * (size_t)nw + 1);                                                             \
-      s_hn.need(2 * (size_t)nw);                                                                   \
-      KLAUNCH((k_walk_spec<NPC, LPC, B>), dim3(nw), dim3(1024), 0, st, t,                         \
-              (const uint16_t*)d_FSS.p, k_len + N, nw, Hcap, s_H.p, s_hn.p, s_hn.p + nw,          \
-              (int4*)s_hres.p, ++walk_epoch, walk_chk[0], walk_chk[1], walk_dbg(nw));              \
-      int32_t* resume = s_hres.p + 4 * nw;                                                         \
-      KLAUNCH(k_walk_join, dim3(64), dim3(256), 0, st, t, (const uint64_t*)s_H.p,                    \
-              (const int32_t*)s_hn.p, (const int4*)s_hres.p, nw, Hcap, k_rs, resume);              \
-      KLAUNCH((k_rounds_walk<NPC, LPC, B>), dim3(1), dim3(1024), 0, st, t,                         \
-              (const uint16_t*)d_FSS.p, k_len, k_len + N, k_rs, 0, 0, dbg_p(),                     \
-              (const int32_t*)resume, RoundAssign{});                                              \
-      if (getenv("HGE_WALK_DEBUG")) walk_debug(nw);                                               \
-    } else {                                                                                       \
-      KLAUNCH((k_rounds_walk<NPC, LPC, B>), dim3(1), dim3(1024), 0, st, t,                         \
-              (const uint16_t*)d_FSS.p, k_len, k_len + N, k_rs, rlo, Rprev, dbg_p(),               \
-              (const int32_t*)nullptr, RoundAssign{});                                             \
-    }                                                                                              \
-  } else {                                                                                         \
-    KLAUNCH(k_fss<NPC>, dim3(div_up((int64_t)tot * NPC, 256)), dim3(256), 0, st, t, k_lo, k_lo + N, \
-            tot, d_FSS.p, (uint16_t*)nullptr, (const int32_t*)nullptr);                            \
-    KLAUNCH(k_rounds_fss<NPC>, dim3(1), dim3(64), 0, st, t, d_FSS.p, k_len, k_len + N, k_rs, rlo);  \
-  }
-            if (NP == 16) {
-              FSSL(16, 4, 256)
-            } else {
-              FSSL(32, 2, 64)
-            }
-#undef FSSL
-          }
-        }
-        }
-      }
-      // rounds, witnesses and the first witness of every round, then ONE round
-      // trip for the round count and minw (the kernels stand down if the rounds
-      // table overflowed: the loop grows it and walks again)
-      t = tables();
-      s_newwit.need(m);
-      if (fresh) {
-        s_newwit.need((size_t)Rcap * N);
-        KLAUNCH(k_round_ranges, dim3(div_up((int64_t)Rcap * N, 256)), dim3(256), 0, st, t, k_len + N,
-                (const int32_t*)k_rs, s_newwit.p, k_rs + 2);
-      } else if (!asg_fused) {
-        // DivideRounds right after (divide()) with nothing coordinated but undivided:
-        // the new ids join the undetermined list here (no k_iota launch)
-        und_appended = dividing && n_divided == n0;
-        KLAUNCH(k_round_assign, dim3(div_up(m, 256)), dim3(256), 0, st, t, (int)n0, (int)n1,
-                (const int32_t*)k_rs, s_newwit.p, k_rs + 2, und_appended ? d_und.p + n_und : (int32_t*)nullptr);
-      }
-      // k_witness_bits (new witnesses' see / strongly-see bitsets) and k_round_minw
-      // (first witness per round, round count, the candidates' lowest round) in one
-      // launch (k_round_tail)
-      // the lowest round of the next batch's candidates (the undetermined list and the
-      // events the next divide appends), read with the round count (a fresh replay's
-      // candidates start at event 0, round 0: nothing to read); an online call's few
-      // candidates are reduced by one extra block of k_round_minw
-      const int64_t n_mr = n_und + (n1 - n_divided);
-      const int mr = tail_fused ? 0
-                     : !fresh && n_mr <= 65536 ? (int)std::max<int64_t>(1, std::min<int64_t>(16, div_up(n_mr, 2048)))
-                                               : 0;
-      if (!tail_fused) {
-        int G = 1;
-        while (G < std::min(N, 64)) G <<= 1;
-        const int64_t wmax = std::min<int64_t>(m, (int64_t)Rcap * N);  // witnesses <= both
-        const int nb_wb = std::max(1, std::min(div_up(wmax * NW * G, 256), 8192));
-        KLAUNCH(k_round_tail, dim3(nb_wb + div_up(Rcap, 4) + mr), dim3(256), 0, st, t, s_newwit.p, k_rs + 2,
-                N > 32 ? (const uint64_t*)d_ssc.p : nullptr, G, nb_wb, (const int32_t*)k_rs, d_minw.p,
-                (const int32_t*)coop_err_src, mr, (const int32_t*)d_und.p, (int)n_und, (int)n_divided, (int)n1);
-      }
-      if (!fresh && !mr && !tail_fused) {
-        if (n_und > 0)
-          KLAUNCH(k_min_round, dim3(div_up(n_und, 256)), dim3(256), 0, st, d_round.p, d_und.p, (int)n_und,
-                  d_minw.p + Rcap + 2);
-        if (n1 > n_divided)
-          KLAUNCH(k_min_round_range, dim3(div_up(n1 - n_divided, 256)), dim3(256), 0, st, d_round.p,
-                  (int)n_divided, (int)n1, d_minw.p + Rcap + 2);
-      }
-      h_minw.resize(Rcap + 4 + mr);
-      d2h(h_minw.data(), d_minw.p, 4 * ((size_t)Rcap + 4 + mr));
-      sync();
-      minw_full = false;  // every round's first witness is in d_minw now
-      if (!fresh) {
-        mnr_pre = h_minw[Rcap + 2];
-        for (int b = 0; b < mr; b++) mnr_pre = std::min(mnr_pre, h_minw[Rcap + 4 + b]);
-      }
-      if (coop_err_check && coop_err_src) coop_err = h_minw[Rcap + 3];
-      coop_err_src = nullptr;
-      mnr_key[0] = fresh ? -1 : n_und;
-      mnr_key[1] = n_divided;
-      mnr_key[2] = n1;
-      if (coop_err_check) {
-        coop_err_check = false;
-        if (coop_err) {
-          // a wide walk's frontier hand-off timed out (its workgroups were not all
-          // resident: another grid on the device, e.g. one engine per rank on a
-          // shared GPU).  The kernels after it stood down; the engine walks again
-          // with k_round_step32, one launch per round, which needs no co-residency,
-          // and keeps that walk from here on.  Rows at and past the rounds this
-          // batch started from are recomputed from scratch.
-          frontier_fallback = true;
-          n_frontier_fallbacks++;
-          HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(d_C.p + (size_t)R * N), INF32, (size_t)(Rcap - R) * N, st));
-          continue;
-        }
-      }
-      if (h_minw[Rcap + 1]) {
+      const int32_t rs[3] = {R, 0, 0};
+      if (retry) h2d(s.rstate, rs, 12);
+      const Walk w = walk_rounds(s);
+      assign_rounds(s, w);
+      const RoundsOutcome o = read_rounds(s, w, rounds_tail(s, w));
+      if (o == RoundsOutcome::HandoffTimeout) {
+        // the walk's workgroups were not all resident (another grid on the device, e.g.
+        // one engine per rank on a shared GPU).  The engine walks again with
+        // k_round_step32, one launch per round, which needs no co-residency, and keeps
+        // that walk from here on.  Rows at and past the rounds this batch started from
+        // are recomputed from scratch.
+        frontier_fallback = true;
+        n_frontier_fallbacks++;
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(d_C.p + (size_t)R * N), INF32, (size_t)(Rcap - R) * N, st));
+      } else if (o == RoundsOutcome::Grow) {
         ensure_rcap((int64_t)Rcap * 2);
-        continue;
+      } else {
+        break;
       }
-      R = h_minw[Rcap];
-      h_minw.resize(R);
-      break;
     }
-    n_coords = n1;
+    n_coords = s.n1;
     coords_len = chain_len;
-    fst_fused = false;
     prof_collect();
+  }
+  Walk walk_rounds(CoordStep& s) {
+    if (N > 32 && (wide32 || frontier_fallback)) return rounds_step32(s);
+    if (N > 32) return rounds_coop(s);
+    if (!s.fresh && s.maxlen < 0xFFFF) return walk_online(s);
+    return walk_fss(s);
+  }
+  // The N <= 32 walks' kernels for rows of 16 or 32 columns, each under the name
+  // KLAUNCH gives the instantiation (hge_kernel_stats keys on it)
+  struct WalkKernels {
+    int NPC;
+    decltype(&k_fss<16>) fss;
+    decltype(&k_rounds_walk<16, 4, 256>) walk;
+    decltype(&k_walk_spec<16, 4, 256>) spec;
+    decltype(&k_rounds_fss<16>) rounds_fss;
+    const char *fss_name, *walk_name, *spec_name, *rounds_fss_name;
+  };
+  const WalkKernels& walk_kernels() const {
+    static const WalkKernels k16{16, k_fss<16>, k_rounds_walk<16, 4, 256>, k_walk_spec<16, 4, 256>, k_rounds_fss<16>,
+                                 "k_fss<16>", "(k_rounds_walk<16, 4, 256>)", "(k_walk_spec<16, 4, 256>)",
+                                 "k_rounds_fss<16>"};
+    static const WalkKernels k32{32, k_fss<32>, k_rounds_walk<32, 2, 64>, k_walk_spec<32, 2, 64>, k_rounds_fss<32>,
+                                 "k_fss<32>", "(k_rounds_walk<32, 2, 64>)", "(k_walk_spec<32, 2, 64>)",
+                                 "k_rounds_fss<32>"};
+    return N <= 16 ? k16 : k32;
+  }
+
+  // N <= 32 past a fresh state, positions below 65,535 (an online call): the walk's
+  // first round, its k_fss rows and their count stay on the device (k_frontier_start
+  // writes them; k_fss loops over the count, k_rounds_walk stands down at INF32): no
+  // round trip.  The walk's block also does k_round_assign's work and, for up to
+  // 65,536 candidates, k_round_tail's.
+  Walk walk_online(CoordStep& s) {
+    const Tables t = tables();
+    const WalkKernels& k = walk_kernels();
+    s_fst.need(N + 1);
+    if (!s.take_frontier_start())  // (else k_la_seq's last block wrote them)
+      KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, s.olen, s.len, s_fst.p, s.fss_lo,
+              (int32_t*)nullptr, (uint64_t*)nullptr, 0);
+    const int64_t guess = (s.n1 - s.n0) + 16 * (int64_t)N;  // the grid loops past it
+    und_appended = dividing && n_divided == s.n0;
+    Walk w;
+    w.assigned = true;
+    w.tail_done = n_und + (s.n1 - n_divided) <= 65536;
+    const RoundAssign ra = round_assign(s, w.tail_done);
+    KLAUNCH_AS(k.fss_name, k.fss, dim3((unsigned)std::min<int64_t>(1024, div_up(guess * k.NPC, 256))), dim3(256), 0,
+               st, t, s.fss_lo, s.fss_off, 0, (int32_t*)nullptr, (uint16_t*)d_FSS.p, (const int32_t*)s.fss_total);
+    KLAUNCH_AS(k.walk_name, k.walk, dim3(1), dim3(1024), 0, st, t, (const uint16_t*)d_FSS.p, s.olen, s.len, s.rstate,
+               0, R, dbg_p(), (const int32_t*)s_fst.p, ra);
+    return w;
+  }
+
+  // N <= 32 from a fresh state (the frontier starts at round 0, position 0), or with a
+  // chain of 65,535 events or more: first-strong-seer rows for every event that can
+  // still be a frontier member, sized by the host (one round trip past a fresh state)
+  Walk walk_fss(CoordStep& s) {
+    const Tables t = tables();
+    const WalkKernels& k = walk_kernels();
+    const int Rprev = R;  // C rows >= Rprev are empty before this batch
+    std::vector<int32_t> fst(N + 1, 0);
+    if (!s.fresh) {
+      s_fst.need(N + 1);
+      KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, s.olen, s.len, s_fst.p, (int32_t*)nullptr,
+              (int32_t*)nullptr, (uint64_t*)nullptr, 0);
+      readback(fst.data(), s_fst.p, N + 1);
+    }
+    const int rlo = fst[0];
+    if (rlo == INF32) return {};
+    int tot = s.fresh ? s.tot0 : 0;
+    if (!s.fresh) {
+      std::vector<int32_t> lo_off(2 * N + 1);
+      for (int c = 0; c < N; c++) {
+        lo_off[c] = fst[1 + c];
+        lo_off[N + c] = tot;
+        tot += std::max(0, chain_len[c] - fst[1 + c]);
+      }
+      lo_off[2 * N] = tot;
+      h2d(s.fss_lo, lo_off.data(), 4 * (2 * N + 1));
+    }
+    if (tot <= 0) return {};
+    // the LDS walk keeps chain positions as uint16; longer chains take the register
+    // walk over the global int32 fss rows
+    const bool long_chain = s.maxlen >= 0xFFFF;
+    KLAUNCH_AS(k.fss_name, k.fss, dim3(div_up((int64_t)tot * k.NPC, 256)), dim3(256), 0, st, t, s.fss_lo, s.fss_off, tot,
+               long_chain ? d_FSS.p : (int32_t*)nullptr, long_chain ? (uint16_t*)nullptr : (uint16_t*)d_FSS.p,
+               (const int32_t*)nullptr);
+    if (long_chain) {
+      KLAUNCH_AS(k.rounds_fss_name, k.rounds_fss, dim3(1), dim3(64), 0, st, t, d_FSS.p, s.olen, s.len, s.rstate, rlo);
+      return {};
+    }
+    const int nw = s.fresh ? spec_walkers(s.minlen) : 0;
+    const int32_t* resume = nw > 1 ? spec_walk(t, s, k, nw) : nullptr;
+    KLAUNCH_AS(k.walk_name, k.walk, dim3(1), dim3(1024), 0, st, t, (const uint16_t*)d_FSS.p, s.olen, s.len, s.rstate,
+               resume ? 0 : rlo, resume ? 0 : Rprev, dbg_p(), resume, RoundAssign{});
+    if (resume && getenv("HGE_WALK_DEBUG")) walk_debug(nw);
+    return {};
+  }
+  // the speculative walkers (hge_walk_spec.hip) and their join; returns the join's resume row
+  const int32_t* spec_walk(const Tables& t, const CoordStep& s, const WalkKernels& k, int nw) {
+    const char* hc = getenv("HGE_WALK_HCAP");  // tests: force the capacity fallback
+    const int Hcap = hc ? std::max(2, atoi(hc)) : std::max(256, std::min(Rcap, 3 * (Rcap / nw) + 256));
+    if ((size_t)nw * Hcap * N > s_H.n) {
+      s_H.need((size_t)nw * Hcap * N);  // epoch 0 never matches a launch's tag
+      HIPCHK(hipMemsetAsync(s_H.p, 0, s_H.n * sizeof(uint64_t), st));
+    }
+    s_hres.need(4 * (size_t)nw + 1);
+    s_hn.need(2 * (size_t)nw);
+    KLAUNCH_AS(k.spec_name, k.spec, dim3(nw), dim3(1024), 0, st, t, (const uint16_t*)d_FSS.p, s.len, nw, Hcap, s_H.p,
+               s_hn.p, s_hn.p + nw, (int4*)s_hres.p, ++walk_epoch, walk_chk[0], walk_chk[1], walk_dbg(nw));
+    int32_t* resume = s_hres.p + 4 * nw;
+    KLAUNCH(k_walk_join, dim3(64), dim3(256), 0, st, t, (const uint64_t*)s_H.p, (const int32_t*)s_hn.p,
+            (const int4*)s_hres.p, nw, Hcap, s.rstate, resume);
+    return resume;
+  }
+  // rounds and witnesses of the new events, unless the walk's block assigned them
+  void assign_rounds(const CoordStep& s, const Walk& w) {
+    const Tables t = tables();
+    const int m = (int)(s.n1 - s.n0);
+    s_newwit.need(m);
+    if (s.fresh) {
+      s_newwit.need((size_t)Rcap * N);
+      KLAUNCH(k_round_ranges, dim3(div_up((int64_t)Rcap * N, 256)), dim3(256), 0, st, t, s.len,
+              (const int32_t*)s.rstate, s_newwit.p, s.rstate + 2);
+    } else if (!w.assigned) {
+      // DivideRounds right after (divide()) with nothing coordinated but undivided:
+      // the new ids join the undetermined list here (no k_iota launch)
+      und_appended = dividing && n_divided == s.n0;
+      KLAUNCH(k_round_assign, dim3(div_up(m, 256)), dim3(256), 0, st, t, (int)s.n0, (int)s.n1,
+              (const int32_t*)s.rstate, s_newwit.p, s.rstate + 2, und_appended ? d_und.p + n_und : (int32_t*)nullptr);
+    }
+  }
+  // k_round_tail, unless the walk's block did its work: the new witnesses' see /
+  // strongly-see bitsets, the first witness per round, the round count, and the lowest
+  // round of the next batch's candidates (the undetermined list and the events the next
+  // divide appends; none to read on a fresh replay).  An online call's few candidates
+  // are reduced by `mr` extra blocks (returned), more by the k_min_round pair.
+  int rounds_tail(const CoordStep& s, const Walk& w) {
+    if (w.tail_done) return 0;
+    const Tables t = tables();
+    const int m = (int)(s.n1 - s.n0), G = wit_group();
+    const int64_t n_mr = n_und + (s.n1 - n_divided);
+    const int mr = !s.fresh && n_mr <= 65536 ? (int)std::max<int64_t>(1, std::min<int64_t>(16, div_up(n_mr, 2048))) : 0;
+    const int64_t wmax = std::min<int64_t>(m, (int64_t)Rcap * N);  // witnesses <= both
+    const int nb_wb = std::max(1, std::min(div_up(wmax * NW * G, 256), 8192));
+    KLAUNCH(k_round_tail, dim3(nb_wb + div_up(Rcap, 4) + mr), dim3(256), 0, st, t, s_newwit.p, s.rstate + 2,
+            N > 32 ? (const uint64_t*)d_ssc.p : nullptr, G, nb_wb, (const int32_t*)s.rstate, d_minw.p, w.err_src, mr,
+            (const int32_t*)d_und.p, (int)n_und, (int)n_divided, (int)s.n1);
+    if (!s.fresh && !mr) {
+      int32_t* mnr = d_minw.p + Rcap + hge_plan::kTailMinRound;
+      if (n_und > 0)
+        KLAUNCH(k_min_round, dim3(div_up(n_und, 256)), dim3(256), 0, st, d_round.p, d_und.p, (int)n_und, mnr);
+      if (s.n1 > n_divided)
+        KLAUNCH(k_min_round_range, dim3(div_up(s.n1 - n_divided, 256)), dim3(256), 0, st, d_round.p,
+                (int)n_divided, (int)s.n1, mnr);
+    }
+    return mr;
+  }
+  // the one readback: the rounds' first witnesses and the tail words behind them
+  RoundsOutcome read_rounds(const CoordStep& s, const Walk& w, int mr) {
+    h_minw.resize(Rcap + hge_plan::kTailPartial + mr);
+    d2h(h_minw.data(), d_minw.p, 4 * h_minw.size());
+    sync();
+    minw_full = false;  // every round's first witness is in d_minw now
+    const hge_plan::RoundsTail r = hge_plan::parse_rounds_tail(h_minw.data() + Rcap, mr);
+    if (!s.fresh) mnr_pre = r.min_round;
+    mnr_key[0] = s.fresh ? -1 : n_und;
+    mnr_key[1] = n_divided;
+    mnr_key[2] = s.n1;
+    if (w.err_src ? r.handoff_err != 0 : w.host_err) return RoundsOutcome::HandoffTimeout;
+    if (r.overflow) return RoundsOutcome::Grow;
+    R = r.R;
+    h_minw.resize(R);
+    return RoundsOutcome::Done;
   }
 
   // Walkers of the speculative frontier walk (hge_walk_spec.hip) for a fresh
   // state: one per ~192 positions of the shortest chain, up to 32 (HGE_WALKERS
   // overrides; 0 or 1 = the sequential walk).  Short graphs walk sequentially.
-  int spec_walkers(int maxlen) {
+  int spec_walkers(int minlen) {
     const char* ev = getenv("HGE_WALKERS");  // read per call: the tests vary it
     const int env = ev ? atoi(ev) : -1;
-    int minlen = INT32_MAX;
-    for (int c = 0; c < N; c++) minlen = std::min(minlen, chain_len[c]);
     const int nw = env >= 0 ? env : (minlen >= 4 * 192 ? std::min(32, minlen / 192) : 0);
     return std::max(0, std::min(nw, 64));
   }
@@ -1365,11 +1372,10 @@ struct hge_engine {
     fprintf(stderr, "\n");
   }
 
-  // rounds of a wide hashgraph: cooperative frontier kernel (hge_rounds_coop.hip)
   // Speculative walkers of the wide walk (fresh state, N <= 128): as many
   // N-workgroup walkers as stay co-resident, up to 8; HGE_COOP_WALKERS overrides
   // (read per call: the tests vary it; 0 or 1 = the sequential kernel alone).
-  int coop_walkers() {
+  int coop_walkers(int minlen) {
     // walker block size: 512 threads x 2 per CU at N <= 64, 1024 x 1 above (means over
     // seeds 1-3, profiles/r01/specbs: 113.3 vs 106.4M ev/s at 64/1M, 60.8 vs 62.9M at 128/1M)
     const int sbs = N > 64 ? 1024 : COOP_SPEC_BS;
@@ -1378,8 +1384,6 @@ struct hge_engine {
       HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&coop_spec_nb, coop_spec_fn(), sbs, 0));
     }
     const int cap = (int)std::min<int64_t>(16, (int64_t)coop_spec_nb * coop_ncu / N);
-    int minlen = INT32_MAX;
-    for (int c = 0; c < N; c++) minlen = std::min(minlen, chain_len[c]);
     const char* ev = getenv("HGE_COOP_WALKERS");
     // above N = 128 only 2 walkers fit, and the 512-thread sequential kernel is faster
     // than 2 walkers sharing each CU (22.5 vs 33.6 ms at 256/2M, profiles/r01r_*)
@@ -1430,150 +1434,160 @@ struct hge_engine {
   // hge_rounds_coop.hip.
   bool direct_rounds() const { return (N & 3) == 0; }
 
-
-  // rounds of a wide hashgraph: cooperative frontier kernel (hge_rounds_coop.hip)
-  // (the caller holds frontier_lock() until the stream has drained)
-  int32_t coop_err = 0;
-  bool coop_err_check = false;
-  const int32_t* coop_err_src = nullptr;  // the walk's error flag on the device (read with minw)
+  // rounds of a wide hashgraph: the frontier start, a split run's joined rows or the speculative
+  // walkers, then the walk's one grid (the caller holds frontier_lock() until the stream has drained)
   bool frontier_fallback = false;  // k_round_step32 for good after a hand-off timeout
   int64_t n_frontier_fallbacks = 0;
-  void rounds_coop(bool fresh) {
-    Tables t = tables();
+  Walk rounds_coop(CoordStep& s) {
+    const Tables t = tables();
     s_fst.need(N + 1);
     // (the hand-off flags and granules are zeroed by k_frontier_start)
     s_bar.need(2);
     s_gran.need(2 * (size_t)N);
-    if (!fst_fused || fresh)  // (else the chain fill's last block ran it)
-      KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, k_len, k_len + N, s_fst.p, (int32_t*)nullptr,
+    if (!s.take_frontier_start())  // (else the chain fill's last block ran it)
+      KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, s.olen, s.len, s_fst.p, (int32_t*)nullptr,
               s_bar.p, (uint64_t*)s_gran.p, 2 * N);
-    fst_fused = false;
     // the lowest round to recompute: read back for a fresh state (the walkers and the
     // joined rows need it on the host), else read by the frontier kernel itself,
     // which stands down at INF32 (no round trip)
-    int32_t rlo = 0;
-    const int32_t* rlo_dev = nullptr;
-    if (fresh) {
-      rlo = INF32;
-      readback(&rlo, s_fst.p, 1);
-      if (rlo == INF32) return;
-    } else {
-      rlo_dev = s_fst.p;
+    int32_t rlo = s.fresh ? INF32 : 0;
+    const int32_t* rlo_dev = s.fresh ? nullptr : s_fst.p;
+    if (s.fresh) readback(&rlo, s_fst.p, 1);
+    if (rlo == INF32) return {};
+    const int Rprev = R;
+    if (!coop_resident()) {  // a device too small for the walk's grid
+      frontier_fallback = true;
+      return rounds_step32(s);
     }
-    int Rprev = R;
-    if (!coop_checked) {
-      int nb = 0, ncu = 0, coop = 0;
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_rounds_coop, COOP_BS, 0));
-      HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-      HIPCHK(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, device));
-      if (!coop || (int64_t)nb * ncu < N) {  // a device too small for the walk's grid
-        frontier_fallback = true;
-        rounds_step32();
-        return;
-      }
-      coop_nb = nb;
-      coop_ncu = ncu;
-      coop_checked = true;
-    }
-    int maxlen = 0;
-    for (int c = 0; c < N; c++) maxlen = std::max(maxlen, chain_len[c]);
     // admission switches the engine to int32 positions (to_wide32) before a chain
     // passes 65,534 events, so this packed walk never sees one; the check guards it
-    if (maxlen >= 0xFFFF)
+    if (s.maxlen >= 0xFFFF)
       throw EngineError(HGE_ERR_INTERNAL, "packed rounds walk reached a chain past 65,534 events");
-    const int32_t* FDT = d_FDT.p;
-    const int32_t* olen = k_len;
-    const int32_t* len = k_len + N;
-    int32_t* rstate = k_rs;
-    int32_t* err = s_bar.p + 1;
-    if (ext_on && fresh && rlo == 0 && Rprev == 0) {
-      // frontier rows joined from the walkers of all ranks (babble_amd/dist.py)
-      const int K = ext_rows;  // true rows 0 .. K-1
-      if (K + 1 >= Rcap) {  // the rounds table must hold them: overflow, grow, come back
-        int32_t ov[2] = {0, 1};
-        h2d(rstate, ov, 8);
-        return;
-      }
-      ext_on = false;
-      h2d(d_C.p, ext_C.data(), sizeof(int32_t) * (size_t)K * N);
-      if (K > 1) h2d(d_ssc.p + (size_t)N * NW, ext_ssc.data() + (size_t)N * NW, sizeof(uint64_t) * (size_t)(K - 1) * N * NW);
-      if (ext_natural) {  // the walk ended: row K is the empty frontier
-        int32_t rs0 = K;
-        h2d(rstate, &rs0, 4);
-        return;
-      }
-      rlo = K - 1;  // the sequential walk resumes from the last true row
-    }
-    const int nw = (fresh && rlo == 0 && Rprev == 0) ? coop_walkers() : 0;
+    const bool from_zero = s.fresh && rlo == 0 && Rprev == 0;
+    if (ext_on && from_zero && install_ext_rows(s, rlo)) return {};
+    Walk w;
+    const int nw = from_zero && rlo == 0 ? coop_walkers(s.minlen) : 0;  // (the joined rows may have moved rlo)
     if (nw >= 2) {
-      const char* hc = getenv("HGE_WALK_HCAP");  // tests: force the capacity fallback
-      const int Hcap = hc ? std::max(2, std::min(0xFFFF, atoi(hc)))
-                          : std::min(0xFFFF, std::min(Rcap, std::max(256, 3 * (Rcap / nw) + 256)));
-      int TS = 64;
-      while (TS < 2 * Hcap) TS <<= 1;
-      const size_t nh = (size_t)nw * Hcap * N, nt = (size_t)nw * TS;
-      const size_t hn0 = s_cH.n, tn0 = s_cT.n;  // a new allocation holds arbitrary words
-      s_cH.need(nh);
-      s_cT.need(nt);
-      bool clear = s_cH.n != hn0 || s_cT.n != tn0;
-      if (++coop_epoch >= 0x7FFFFFFFu) {  // tags wrap: clear, restart at 1
-        coop_epoch = 1;
-        clear = true;
-      }
-      if (clear) {
-        HIPCHK(hipMemsetAsync(s_cH.p, 0, s_cH.n * sizeof(uint64_t), st));
-        HIPCHK(hipMemsetAsync(s_cT.p, 0, s_cT.n * sizeof(uint64_t), st));
-      }
-      s_cS.need(nh * NW);
-      s_cM.need(nw);
-      s_cn.need(2 * (size_t)nw + 1);
-      HIPCHK(hipMemsetAsync(s_cM.p, 0xFF, (size_t)nw * sizeof(uint64_t), st));
-      int64_t nev = 0;
-      for (int c = 0; c < N; c++) nev += chain_len[c];
-      // guesses (measured over seeds 1-3, profiles/r01/guess128): time cuts at N <= 64,
-      // alternating length/time cuts above
-      const int guess = N <= 64 ? 1 : 2;
-      CoopSpec cs{s_cH.p, s_cS.p, s_cT.p, (unsigned long long*)s_cM.p, s_cn.p, nw, Hcap, TS,
-                  coop_epoch, nev, guess};
-      void* sargs[] = {&t, &FDT, &olen, &len, &cs, &err};
-      prof_begin("k_rounds_coop_spec");
-      HIPCHK(launch_resident(coop_spec_fn(), dim3(nw * N), dim3(coop_spec_bs), sargs));
-      prof_end();
-      int32_t* resume = s_cn.p + 2 * nw;
-      KLAUNCH(k_coop_join, dim3(64), dim3(256), 0, st, t, cs, d_ssc.p, rstate, resume);
-      int32_t hres[2] = {0, 0};
-      readback(&hres[0], err, 1);
-      if (hres[0]) {  // co-residency failure: coords_b falls back to k_round_step32
-        const int32_t down[2] = {Rprev, 4};
-        h2d(rstate, down, 8);
-        coop_err = 1;
-        coop_err_check = true;
-        coop_err_src = nullptr;
-        return;
-      }
-      readback(&hres[1], resume, 1);
-      if (getenv("HGE_WALK_DEBUG")) {
-        std::vector<int32_t> hn(2 * nw);
-        std::vector<uint64_t> mg(nw);
-        readback(hn.data(), s_cn.p, hn.size());
-        readback(mg.data(), s_cM.p, mg.size());
-        fprintf(stderr, "coop walk: nw=%d Hcap=%d resume=%d |", nw, Hcap, hres[1]);
-        for (int w = 0; w < nw; w++)
-          fprintf(stderr, " %d:%d%s->(%d,w%d:%d)", w, hn[w], hn[nw + w] ? "e" : "",
-                  mg[w] == ~0ull ? -1 : (int)(mg[w] >> 32),
-                  mg[w] == ~0ull ? -1 : w + (int)((mg[w] >> 16) & 0xFFFF), (int)(mg[w] & 0xFFFF));
-        fprintf(stderr, "\n");
-      }
-      if (hres[1] < 0) return;
-      rlo = hres[1];
+      const int resume = coop_spec_walk(t, s, nw, Rprev, w);
+      if (resume < 0) return w;
+      rlo = resume;
     }
+    wide_walk(t, s, rlo, rlo_dev, Rprev);
+    // the hand-off error flag comes back with the round count (read_rounds, k_round_tail)
+    w.err_src = s_bar.p + 1;
+    dbg_dump();
+    return w;
+  }
+  // the walk's grid must fit the device at once: checked once with the occupancy API
+  bool coop_resident() {
+    if (coop_checked) return true;
+    int nb = 0, ncu = 0, coop = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_rounds_coop, COOP_BS, 0));
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    HIPCHK(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, device));
+    if (!coop || (int64_t)nb * ncu < N) return false;
+    coop_nb = nb;
+    coop_ncu = ncu;
+    coop_checked = true;
+    return true;
+  }
+  // frontier rows joined from the walkers of all ranks (babble_amd/dist.py); true:
+  // nothing is left to walk (rstate says why), else rlo is the row to resume from
+  bool install_ext_rows(const CoordStep& s, int32_t& rlo) {
+    const int K = ext_rows;  // true rows 0 .. K-1
+    if (K + 1 >= Rcap) {  // the rounds table must hold them: overflow, grow, come back
+      const int32_t ov[2] = {0, hge_plan::kRoundsFull};
+      h2d(s.rstate, ov, 8);
+      return true;
+    }
+    ext_on = false;
+    h2d(d_C.p, ext_C.data(), sizeof(int32_t) * (size_t)K * N);
+    if (K > 1) h2d(d_ssc.p + (size_t)N * NW, ext_ssc.data() + (size_t)N * NW, sizeof(uint64_t) * (size_t)(K - 1) * N * NW);
+    if (ext_natural) {  // the walk ended: row K is the empty frontier
+      const int32_t rs0 = K;
+      h2d(s.rstate, &rs0, 4);
+      return true;
+    }
+    rlo = K - 1;  // the sequential walk resumes from the last true row
+    return false;
+  }
+  // the wide walk's speculative walkers and their join; returns the row to resume from,
+  // < 0: nothing left to walk (every round covered, or a hand-off timeout: w.host_err)
+  int coop_spec_walk(Tables t, const CoordStep& s, int nw, int Rprev, Walk& w) {
+    const int32_t* FDT = d_FDT.p;
+    const int32_t* olen = s.olen;
+    const int32_t* len = s.len;
+    int32_t* err = s_bar.p + 1;
+    const char* hc = getenv("HGE_WALK_HCAP");  // tests: force the capacity fallback
+    const int Hcap = hc ? std::max(2, std::min(0xFFFF, atoi(hc)))
+                        : std::min(0xFFFF, std::min(Rcap, std::max(256, 3 * (Rcap / nw) + 256)));
+    int TS = 64;
+    while (TS < 2 * Hcap) TS <<= 1;
+    const size_t nh = (size_t)nw * Hcap * N, nt = (size_t)nw * TS;
+    const size_t hn0 = s_cH.n, tn0 = s_cT.n;  // a new allocation holds arbitrary words
+    s_cH.need(nh);
+    s_cT.need(nt);
+    bool clear = s_cH.n != hn0 || s_cT.n != tn0;
+    if (++coop_epoch >= 0x7FFFFFFFu) {  // tags wrap: clear, restart at 1
+      coop_epoch = 1;
+      clear = true;
+    }
+    if (clear) {
+      HIPCHK(hipMemsetAsync(s_cH.p, 0, s_cH.n * sizeof(uint64_t), st));
+      HIPCHK(hipMemsetAsync(s_cT.p, 0, s_cT.n * sizeof(uint64_t), st));
+    }
+    s_cS.need(nh * NW);
+    s_cM.need(nw);
+    s_cn.need(2 * (size_t)nw + 1);
+    HIPCHK(hipMemsetAsync(s_cM.p, 0xFF, (size_t)nw * sizeof(uint64_t), st));
+    int64_t nev = 0;
+    for (int c = 0; c < N; c++) nev += chain_len[c];
+    // guesses (measured over seeds 1-3, profiles/r01/guess128): time cuts at N <= 64,
+    // alternating length/time cuts above
+    const int guess = N <= 64 ? 1 : 2;
+    CoopSpec cs{s_cH.p, s_cS.p, s_cT.p, (unsigned long long*)s_cM.p, s_cn.p, nw, Hcap, TS,
+                coop_epoch, nev, guess};
+    void* sargs[] = {&t, &FDT, &olen, &len, &cs, &err};
+    prof_begin("k_rounds_coop_spec");
+    HIPCHK(launch_resident(coop_spec_fn(), dim3(nw * N), dim3(coop_spec_bs), sargs));
+    prof_end();
+    int32_t* resume = s_cn.p + 2 * nw;
+    KLAUNCH(k_coop_join, dim3(64), dim3(256), 0, st, t, cs, d_ssc.p, s.rstate, resume);
+    int32_t hres[2] = {0, 0};
+    readback(&hres[0], err, 1);
+    if (hres[0]) {  // co-residency failure: coords_b falls back to k_round_step32
+      const int32_t down[2] = {Rprev, hge_plan::kRoundsStoodDown};
+      h2d(s.rstate, down, 8);
+      w.host_err = true;
+      return -1;
+    }
+    readback(&hres[1], resume, 1);
+    if (getenv("HGE_WALK_DEBUG")) {
+      std::vector<int32_t> hn(2 * nw);
+      std::vector<uint64_t> mg(nw);
+      readback(hn.data(), s_cn.p, hn.size());
+      readback(mg.data(), s_cM.p, mg.size());
+      fprintf(stderr, "coop walk: nw=%d Hcap=%d resume=%d |", nw, Hcap, hres[1]);
+      for (int i = 0; i < nw; i++)
+        fprintf(stderr, " %d:%d%s->(%d,w%d:%d)", i, hn[i], hn[nw + i] ? "e" : "",
+                mg[i] == ~0ull ? -1 : (int)(mg[i] >> 32),
+                mg[i] == ~0ull ? -1 : i + (int)((mg[i] >> 16) & 0xFFFF), (int)(mg[i] & 0xFFFF));
+      fprintf(stderr, "\n");
+    }
+    return hres[1];
+  }
+  // the wide walk's one grid: direct (N % 4 == 0) or the FDT-gather selection
+  void wide_walk(Tables t, const CoordStep& s, int32_t rlo, const int32_t* rlo_dev, int Rprev) {
+    const int32_t* FDT = d_FDT.p;
+    const int32_t* olen = s.olen;
+    const int32_t* len = s.len;
+    int32_t* rstate = s.rstate;
+    int32_t* err = s_bar.p + 1;
     uint64_t* gran = s_gran.p;
     uint64_t* ssc = d_ssc.p;
     uint64_t* dbg = dbg_p();
     if (direct_rounds()) {
-      // strongly-see tiles on the coordinate rows (hge_rounds_direct.hip)
-      const int npow = N <= 64 ? 64 : N <= 128 ? 128 : 256;
-      s_mb.need((size_t)npow * npow);  // two parity blocks of npow rows x npow/2 packed words
+      s_mb.need((size_t)npow() * npow());  // two parity blocks of npow rows x npow/2 packed words
       uint32_t* mb = s_mb.p;
       const int32_t* nostart = nullptr;
       int32_t* nohist = nullptr;
@@ -1583,11 +1597,8 @@ struct hge_engine {
       int stall_ep = hs ? atoi(hs) : 0;
       void* dargs[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
                        &nostart, &nohist, &hmax, &nostart, &extra, &stall_ep};
-      const void* fn = N <= 64 ? (const void*)k_rounds_direct<1024, 64>
-                     : N <= 128 ? (const void*)k_rounds_direct<1024, 128>
-                                : (const void*)k_rounds_direct<1024, 256>;
       prof_begin("k_rounds_direct");
-      HIPCHK(launch_resident(fn, dim3(N), dim3(1024), dargs));
+      HIPCHK(launch_resident(direct_fn(), dim3(N), dim3(1024), dargs));
       prof_end();
     } else {
       void* args[] = {&t, &FDT, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &dbg};
@@ -1596,14 +1607,15 @@ struct hge_engine {
       prof_end();
     }
     if (getenv("HGE_TEST_HANDOFF_FAIL")) {  // tests: the walk reports a hand-off timeout
-      const int32_t one = 1, down = 4;
+      const int32_t one = 1, down = hge_plan::kRoundsStoodDown;
       h2d(err, &one, 4);
       h2d(rstate + 1, &down, 4);
     }
-    // the hand-off error flag comes back with the round count (coords_b, k_round_minw)
-    coop_err_src = s_bar.p + 1;
-    coop_err_check = true;
-    dbg_dump();
+  }
+  const void* direct_fn() const {
+    return N <= 64 ? (const void*)k_rounds_direct<1024, 64>
+         : N <= 128 ? (const void*)k_rounds_direct<1024, 128>
+                    : (const void*)k_rounds_direct<1024, 256>;
   }
 
   // N > 32: lastAncestors live in the packed 16-bit table while every chain holds at
@@ -1666,35 +1678,35 @@ struct hge_engine {
 
   // rounds with int32 positions: k_round_step32 round by round from the first round
   // to recompute, 32 launches between readbacks of their "row exists" flags
-  void rounds_step32() {
+  Walk rounds_step32(const CoordStep& s) {
     Tables t = tables();
     s_fst.need(N + 1);
-    KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, k_len, k_len + N, s_fst.p, (int32_t*)nullptr,
+    KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, s.olen, s.len, s_fst.p, (int32_t*)nullptr,
             (int32_t*)nullptr, (uint64_t*)nullptr, 0);
     int32_t rlo = INF32;
     readback(&rlo, s_fst.p, 1);
-    if (rlo == INF32) return;
+    if (rlo == INF32) return {};
     const int Rprev = R, NB = 32;
     s_w32a.need(NB);
     for (int r = rlo;;) {
       HIPCHK(hipMemsetAsync(s_w32a.p, 0, 4 * NB, st));
       int k = 0;
       for (; k < NB && r + k + 1 < Rcap; k++)
-        KLAUNCH(k_round_step32, dim3(N), dim3(256), 0, st, t, (const int32_t*)k_len, (const int32_t*)(k_len + N),
+        KLAUNCH(k_round_step32, dim3(N), dim3(256), 0, st, t, (const int32_t*)s.olen, (const int32_t*)s.len,
                 r + k, Rprev, d_ssc.p, s_w32a.p + k);
       std::vector<int32_t> alive(NB, 0);
       readback(alive.data(), s_w32a.p, NB);
       for (int q = 0; q < k; q++)
         if (!alive[q]) {  // row r + q + 1 is empty: the rounds end there
           const int32_t rs[2] = {std::max(R, r + q + 1), 0};
-          h2d(k_rs, rs, 8);
-          return;
+          h2d(s.rstate, rs, 8);
+          return {};
         }
       r += k;
       if (k < NB) {  // the rounds table is full: grown by the caller, walked again
-        const int32_t rs[2] = {R, 1};
-        h2d(k_rs, rs, 8);
-        return;
+        const int32_t rs[2] = {R, hge_plan::kRoundsFull};
+        h2d(s.rstate, rs, 8);
+        return {};
       }
     }
   }
@@ -1711,11 +1723,11 @@ struct hge_engine {
 
   // passes over windows of the new ids until one changes no row (n_sweeps = passes
   // run); one window is exact in its first pass (its starting rows are final)
-  void la_windows_run(Tables t) {
-    const int32_t* olen = k_len;
-    const int32_t* len = k_len + N;
-    const int64_t n0 = n_coords, n1 = n_events, ne = n1 - n0;
-    const int npow = N <= 64 ? 64 : N <= 128 ? 128 : 256;
+  void la_windows_run(const Tables& t, const CoordStep& s) {
+    const int32_t* olen = s.olen;
+    const int32_t* len = s.len;
+    const int64_t n0 = s.n0, n1 = s.n1, ne = n1 - n0;
+    const int npow = this->npow();
     // k_la_win: one 1024-thread workgroup per window (a barrier-free wave-per-slice
     // variant measured 2x slower: DESIGN.md §4.1)
     const int W = t.NW2;
@@ -1736,7 +1748,7 @@ struct hge_engine {
     // lengths and its risky id starts at -1 in the control block, so k_lw_pos is not
     // needed (one launch less per call)
     const int32_t* wpos = G == 1 ? olen : s_lwpos.p;
-    int32_t* risky = G == 1 ? k_risky1 : s_lwrisky.p;
+    int32_t* risky = G == 1 ? s.risky1 : s_lwrisky.p;
     if (G > 1)
       KLAUNCH(k_lw_pos, dim3(div_up(std::max<int64_t>(G * N, MAXP), 256)), dim3(256), 0, st, t, n0, (int)WN, (int)G,
               len, s_lwpos.p, s_lwrisky.p, s_chg.p, MAXP);
@@ -1772,59 +1784,57 @@ struct hge_engine {
     }
   }
 
-  // coordinates: chain-prefix sweeps + transposes (hge_coords.hip)
   // the one-pass lastAncestors kernel (k_la_seq) takes batches of m new events at N <= 32
   bool la_seq_ok(int64_t m) const {
     return !sweep16() && N <= 32 && m > 0 && m * (N <= 16 ? 16 : 32) <= LASEQ_MAX && !getenv("HGE_NO_LASEQ");
   }
-  const UpEv* fill_up = nullptr;  // coords_a -> the chain-table fill (packed upload or the tables)
-  UpDst fill_dst{};
-  void coords_sweep(Tables t, int nseg, int SEG, int maxnew, bool fresh) {
-    const int32_t* olen = k_len;
-    const int32_t* len = k_len + N;
-    if (nseg == 0) return;
-    // sweeps until one changes nothing; queued in groups, checked once per group
-    // (a sweep after a quiet one returns at once); k_la_clear zeroes the flags
-    const int MAXSW = 4096;
-    s_chg.need(MAXSW);
-    const bool p16 = sweep16();
-    // skip segments whose inputs did not change in the previous sweep
-    const bool SKIP = true;
-    const int64_t mnew = n_events - n_coords;
-    if (p16 && la_windows()) {
-      la_windows_run(t);
-    } else if (la_seq_ok(mnew)) {
-      // a small batch (an online call): one exact pass in insertion order, the chain
-      // table filled by the same kernel
-      // (+ k_fd_qlo's N blocks past a fresh state: coords_b skips its launch)
-      const bool q = !fresh;
-      // (+ k_frontier_start's block when coords_b walks as an online call)
-      int maxlen = 0;
-      for (int c = 0; c < N; c++) maxlen = std::max(maxlen, chain_len[c]);
-      fst_fused = q && maxlen < 0xFFFF;
-      if (fst_fused) s_fst.need(N + 1);
-      int32_t* fp = fst_fused ? s_fst.p : (int32_t*)nullptr;
-      int32_t* fl = fst_fused ? k_lo : (int32_t*)nullptr;
-      // N <= 16 past a fresh state: the batch's firstDescendants in the same launch (no
-      // runs, transpose or k_fd_qlo blocks)
-      fd_direct = q && N <= 16 && !getenv("HGE_NO_FD_DIRECT");
-      const int nq = q && !fd_direct ? N : 0;
-      const int nb = 1 + nq + (fst_fused ? 1 : 0);
-      if (N <= 16)
-        KLAUNCH(k_la_seq<16>, dim3(nb), dim3(256), 0, st, t, (int)n_coords, (int)n_events, fill_up,
-                fill_dst, olen, len, nq ? k_qlo : (int32_t*)nullptr, fp, fl,
-                fd_direct ? d_FDT.p : (int32_t*)nullptr);
-      else
-        KLAUNCH(k_la_seq<32>, dim3(nb), dim3(256), 0, st, t, (int)n_coords, (int)n_events, fill_up,
-                fill_dst, olen, len, nq ? k_qlo : (int32_t*)nullptr, fp, fl, (int32_t*)nullptr);
-      qlo_fused = q;
-      n_sweeps = 1;
+  // lastAncestors of the new events: windows, one pass, or sweeps to the fixed point
+  static constexpr int MAXSW = 4096;  // sweeps at most
+  void last_ancestors(const Tables& t, CoordStep& s) {
+    s_chg.need(MAXSW);  // the passes' "changed" flags
+    if (s.la == CoordStep::La::Windows) {
+      la_windows_run(t, s);
+    } else if (s.la == CoordStep::La::Seq) {
+      la_seq_run(t, s);
     } else {
-    int32_t* dirty = nullptr;
-    if (p16 && SKIP) {
-      s_dirty.need(nseg);
-      dirty = s_dirty.p;
+      la_sweeps_run(t, s);
     }
+  }
+  // a small batch (an online call): one exact pass in insertion order, the chain table
+  // filled by the same kernel
+  void la_seq_run(const Tables& t, CoordStep& s) {
+    // past a fresh state: + k_fd_qlo's N blocks, + k_frontier_start's block when coords_b walks as an online
+    // call; at N <= 16 the batch's firstDescendants in the same launch instead (no runs, transpose, k_fd_qlo)
+    const bool q = !s.fresh, fst = q && s.maxlen < 0xFFFF;
+    const bool fd = q && N <= 16 && !getenv("HGE_NO_FD_DIRECT");
+    if (fst) s_fst.need(N + 1);
+    int32_t* fp = fst ? s_fst.p : (int32_t*)nullptr;
+    int32_t* fl = fst ? s.fss_lo : (int32_t*)nullptr;
+    const int nq = q && !fd ? N : 0;
+    const int nb = 1 + nq + (fst ? 1 : 0);
+    if (N <= 16)
+      KLAUNCH(k_la_seq<16>, dim3(nb), dim3(256), 0, st, t, (int)s.n0, (int)s.n1, s.up, s.up_dst,
+              (const int32_t*)s.olen, (const int32_t*)s.len, nq ? s.qlo : (int32_t*)nullptr, fp, fl,
+              fd ? d_FDT.p : (int32_t*)nullptr);
+    else
+      KLAUNCH(k_la_seq<32>, dim3(nb), dim3(256), 0, st, t, (int)s.n0, (int)s.n1, s.up, s.up_dst,
+              (const int32_t*)s.olen, (const int32_t*)s.len, nq ? s.qlo : (int32_t*)nullptr, fp, fl,
+              (int32_t*)nullptr);
+    s.frontier_started = fst;
+    s.qlo_done = q;
+    s.fd_done = fd;
+    n_sweeps = 1;
+  }
+  // sweeps until one changes nothing; queued in groups, checked once per group
+  // (a sweep after a quiet one returns at once); k_la_clear zeroes the flags
+  void la_sweeps_run(const Tables& t, const CoordStep& s) {
+    const int32_t* olen = s.olen;
+    const int32_t* len = s.len;
+    const int nseg = s.nseg, SEG = s.SEG, maxnew = s.maxnew;
+    const bool p16 = sweep16();
+    // the packed sweeps skip segments whose inputs did not change in the previous sweep
+    if (p16) s_dirty.need(nseg);
+    int32_t* dirty = p16 ? s_dirty.p : nullptr;
     if (p16)
       KLAUNCH(k_la_clear16, dim3(std::max(1, std::min(64, div_up((int64_t)maxnew * t.NW2, 256))), N),
               dim3(256), 0, st, t, olen, len, s_chg.p, MAXSW, dirty, nseg);
@@ -1842,8 +1852,8 @@ struct hge_engine {
           switch (NPt) {
 #define SW16(NPV)                                                                                \
   case NPV:                                                                                      \
-    KLAUNCH(k_la_sweep16<NPV>, dim3(div_up(nseg, 256 / NPV)), dim3(256), 0, st, t, k_segs, nseg, \
-            SEG, len, prev, s_chg.p + sw, olen, k_segbase, dirty, sw);                          \
+    KLAUNCH(k_la_sweep16<NPV>, dim3(div_up(nseg, 256 / NPV)), dim3(256), 0, st, t, s.segs, nseg, \
+            SEG, len, prev, s_chg.p + sw, olen, s.segbase, dirty, sw);                          \
     break;
             SW16(32)
             SW16(64)
@@ -1854,7 +1864,7 @@ struct hge_engine {
           switch (NPt) {
 #define SW(NPV)                                                                                  \
   case NPV:                                                                                      \
-    KLAUNCH(k_la_sweep<NPV>, dim3(div_up(nseg, 256 / NPV)), dim3(256), 0, st, t, k_segs, nseg,   \
+    KLAUNCH(k_la_sweep<NPV>, dim3(div_up(nseg, 256 / NPV)), dim3(256), 0, st, t, s.segs, nseg,   \
             SEG, len, prev, s_chg.p + sw);                                                       \
     break;
             SW(16)
@@ -1874,50 +1884,50 @@ struct hge_engine {
         break;
       }
     }
-    }
-    if (fd_direct) {
-      fd_direct = false;  // (k_la_seq wrote the FD rows and FDT runs)
-      qlo_fused = false;
-      return;
-    }
+  }
+  // firstDescendants: the FDT runs from the LA rows, then FDT -> FD rows
+  void first_descendants(const Tables& t, const CoordStep& s) {
+    if (s.fd_done) return;  // (k_la_seq wrote the FD rows and FDT runs)
+    const int32_t* olen = s.olen;
+    const int32_t* len = s.len;
+    const int maxnew = s.maxnew;
     if (fdt16()) {
       KLAUNCH((k_la16_rows_runs<uint16_t>), dim3(div_up(maxnew + 1, 64), div_up(N, 64), N), dim3(256), 0, st, t,
-              (uint16_t*)d_FDT.p, k_plo, olen, len);
-    } else if (p16) {
+              (uint16_t*)d_FDT.p, s.plo, olen, len);
+    } else if (sweep16()) {
       // LA16 -> the int32 LA rows and the FDT runs from the same tiles (no LAT)
       KLAUNCH((k_la16_rows_runs<int32_t>), dim3(div_up(maxnew + 1, 64), div_up(N, 64), N), dim3(256), 0, st, t,
-              d_FDT.p, k_plo, olen, len);
+              d_FDT.p, s.plo, olen, len);
     } else {
       // the int32 LA rows -> the runs of the new events (and the new positions with no
       // descendant yet) through 64 x 64 LDS tiles (one launch; round 3's LA -> LAT
       // transpose + k_fdt_runs took two and the LAT table)
       KLAUNCH((k_la16_rows_runs<int32_t, true>), dim3(div_up(maxnew + 1, 64), div_up(N, 64), N), dim3(256), 0,
-              st, t, d_FDT.p, k_plo, olen, len);
+              st, t, d_FDT.p, s.plo, olen, len);
     }
     // FDT -> FD rows for every chain-c position a new event can have touched
     // (from a fresh state: every row, qlo = 0 as uploaded; no round trip)
     // (the rows' lower bounds stay on the device: the transposes loop over position
     // tiles past their grid, sized here for the new positions plus a tile)
     int span = 1;
-    if (!fresh) {
-      if (!qlo_fused) KLAUNCH(k_fd_qlo, dim3(N), dim3(256), 0, st, t, olen, len, k_qlo);
-      qlo_fused = false;
+    if (!s.fresh) {
+      if (!s.qlo_done) KLAUNCH(k_fd_qlo, dim3(N), dim3(256), 0, st, t, olen, len, s.qlo);
       span = maxnew + 64;
     } else {
-      for (int c = 0; c < N; c++) span = std::max(span, chain_len[c]);
+      span = std::max(span, s.maxlen);
     }
     // (a split part writes the timestamp rows of its own candidates only)
     if (fdt16())
       KLAUNCH((k_fd_transpose_ts<uint16_t>), dim3(N, div_up(N, 64), std::min(div_up(span, 64), 65535)), dim3(256),
-              0, st, t, (const uint16_t*)d_FDT.p, k_qlo, len, (const int32_t*)k_fd,
-              (const int32_t*)(k_fd ? k_fd + N : nullptr));
+              0, st, t, (const uint16_t*)d_FDT.p, s.qlo, len, (const int32_t*)s.cand_lo,
+              (const int32_t*)s.cand_hi);
     else if (N > 16)
       KLAUNCH((k_fd_transpose_ts<int32_t>), dim3(N, div_up(N, 64), std::min(div_up(span, 64), 65535)), dim3(256),
-              0, st, t, (const int32_t*)d_FDT.p, k_qlo, len, (const int32_t*)k_fd,
-              (const int32_t*)(k_fd ? k_fd + N : nullptr));
+              0, st, t, (const int32_t*)d_FDT.p, s.qlo, len, (const int32_t*)s.cand_lo,
+              (const int32_t*)s.cand_hi);
     else
       KLAUNCH(k_transpose, dim3(div_up(span, 64), div_up(N, 64), N), dim3(256), 0, st, t, d_FDT.p,
-              (int32_t*)nullptr, k_qlo, len, 1);
+              (int32_t*)nullptr, s.qlo, len, 1);
   }
 
   // ---------------- one batch of consensus calls ----------------
@@ -2759,17 +2769,17 @@ struct hge_engine {
   // per-round timeline (else k_fame_call<.., false> takes it)
   void fame_decide(const Tables& t, const hge_plan::FameWindows& w, int npairs, bool timeline = true) {
     const int nrounds = w.nrounds();
-    int k_lo = 0, k_hi = nrounds;
-    if (split_on()) split_rounds_of(sp.part, w.round, k_lo, k_hi);
-    const int p0 = k_lo < nrounds ? w.off[k_lo] : npairs;
-    const int p1 = k_hi < nrounds ? w.off[k_hi] : npairs;
+    int win_lo = 0, win_hi = nrounds;
+    if (split_on()) split_rounds_of(sp.part, w.round, win_lo, win_hi);
+    const int p0 = win_lo < nrounds ? w.off[win_lo] : npairs;
+    const int p1 = win_hi < nrounds ? w.off[win_hi] : npairs;
     if (p1 > p0 && N == 64 * NW) {
-      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3(p1 - p0), dim3(N), 0, st, t, c_pr + k_lo,
-                 c_pr + nrounds + k_lo, c_pr + 2 * nrounds + k_lo, k_hi - k_lo, p0, p1, c_nc, c_Rc, s_dec.p,
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3(p1 - p0), dim3(N), 0, st, t, c_pr + win_lo,
+                 c_pr + nrounds + win_lo, c_pr + 2 * nrounds + win_lo, win_hi - win_lo, p0, p1, c_nc, c_Rc, s_dec.p,
                  (const int32_t*)nullptr);
     } else if (p1 > p0) {
-      KLAUNCH_NW(NW, NW_PT, k_fame_decide, dim3(div_up((p1 - p0) * N, 256)), dim3(256), 0, st, t, c_pr + k_lo,
-                 c_pr + nrounds + k_lo, c_pr + 2 * nrounds + k_lo, k_hi - k_lo, p0, p1, c_nc, c_Rc, s_dec.p);
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide, dim3(div_up((p1 - p0) * N, 256)), dim3(256), 0, st, t, c_pr + win_lo,
+                 c_pr + nrounds + win_lo, c_pr + 2 * nrounds + win_lo, win_hi - win_lo, p0, p1, c_nc, c_Rc, s_dec.p);
     }
     if (split_on()) split_exchange_dec(w.round, w.off, npairs);
     if (!timeline) return;
@@ -2850,12 +2860,10 @@ struct hge_engine {
   // fit this path.
   bool online_fast(std::vector<int32_t>& order) {
     const int64_t n0 = n_coords, n1 = n_events, m = n1 - n0;
-    if (N > 16 || m <= 0 || R == 0 || cs_pending || split_on() || rec_on || ext_on || sp_active) return false;
+    if (N > 16 || m <= 0 || R == 0 || cstep || split_on() || rec_on || ext_on || sp_active) return false;
     if (n_divided != n0 || !la_seq_ok(m) || n_und + m > 65536 || n_und + m > SCAN_LDS) return false;
     if (getenv("HGE_NO_ONLINE_FAST")) return false;
-    int maxlen = 0;
-    for (int c = 0; c < N; c++) maxlen = std::max(maxlen, chain_len[c]);
-    if (maxlen + 1 >= 0xFFFF) return false;
+    if (*std::max_element(chain_len.begin(), chain_len.end()) + 1 >= 0xFFFF) return false;
     consensus_sync();
     ensure_rcap((int64_t)R + m + 4);
     // ---- divide(): coordinates and rounds, no readback
@@ -2865,17 +2873,13 @@ struct hge_engine {
       dividing = false;
       throw EngineError(HGE_ERR_INTERNAL, "online call: no coordinates to compute");
     }
-    if (!fst_fused || !cs_pending) throw EngineError(HGE_ERR_INTERNAL, "online call: frontier start not fused");
-    cs_pending = false;
-    Tables t = tables();
-    und_appended = true;  // (n_divided == n0: the walk's block appends the new ids)
-    const RoundAssign ra = round_assign(n0, n1, true);
-    const int64_t guess = m + 16 * (int64_t)N;
-    KLAUNCH(k_fss<16>, dim3((unsigned)std::min<int64_t>(1024, div_up(guess * 16, 256))), dim3(256), 0, st, t, k_lo,
-            k_lo + N, 0, (int32_t*)nullptr, (uint16_t*)d_FSS.p, (const int32_t*)(k_lo + 2 * N));
-    KLAUNCH((k_rounds_walk<16, 4, 256>), dim3(1), dim3(1024), 0, st, t, (const uint16_t*)d_FSS.p, k_len, k_len + N,
-            k_rs, 0, R, dbg_p(), (const int32_t*)s_fst.p, ra);
-    fst_fused = false;
+    if (!cstep || !cstep->frontier_started)
+      throw EngineError(HGE_ERR_INTERNAL, "online call: frontier start not fused");
+    CoordStep s = *cstep;
+    cstep.reset();
+    // (n_divided == n0 and at most 65,536 candidates: the walk's block appends the new
+    // ids, assigns their rounds and does the rounds tail)
+    walk_online(s);
     dividing = false;
     n_coords = n1;
     coords_len = chain_len;
@@ -2912,7 +2916,7 @@ struct hge_engine {
     dc.ncand = b.ncand;
     dc.Rcap = Rcap;
     dc.n_c = n_divided;
-    dc.rstate = k_rs;
+    dc.rstate = s.rstate;
     dc.minw = d_minw.p;
     dc.c_nc = c_nc;
     dc.c_Rc = c_Rc;
@@ -2927,19 +2931,19 @@ struct hge_engine {
     dc.clast = s_clast.p;
     dc.out = s_out.p;
     dc.o = order_call(b, 1);  // (the buffers; the kernel sets the rounds, the windows and front)
-    t = tables();
-    KLAUNCH(k_consensus_dyn<16>, dim3(1), dim3(1024), 0, st, t, dc);
+    KLAUNCH(k_consensus_dyn<16>, dim3(1), dim3(1024), 0, st, tables(), dc);
     std::swap(d_und, s_und2);
     // ---- the one round trip: the results block and the rounds' first witnesses
     const size_t off = d2h_pinned(s_out.p, 4 * b.out.total());
-    const size_t offw = d2h_pinned(d_minw.p, 4 * ((size_t)Rcap + 4));
+    const size_t offw = d2h_pinned(d_minw.p, 4 * ((size_t)Rcap + hge_plan::kTailPartial));
     sync();
     const int32_t* hw = (const int32_t*)(pin + offw);
-    if (hw[Rcap + 1]) {  // (unreachable: ensure_rcap covers R + m + 4) the host state has moved on: refuse later calls
+    const hge_plan::RoundsTail rt = hge_plan::parse_rounds_tail(hw + Rcap, 0);
+    if (rt.overflow) {  // (unreachable: ensure_rcap covers R + m + 4) the host state has moved on: refuse later calls
       failed = "online call: rounds table overflow past its bound";
       throw EngineError(HGE_ERR_INTERNAL, failed);
     }
-    R = hw[Rcap];
+    R = rt.R;
     h_minw.assign(hw, hw + R);
     minw_full = false;
     mnr_key[0] = -1;
@@ -3162,7 +3166,7 @@ static void replay_begin(hge_engine* h) {
 
 static void replay_end(hge_engine* h, int64_t* n_ordered) {
   const int64_t keep = h->n_events;
-  if (h->cs_pending) h->coords_b();
+  if (h->cstep) h->coords_b();
   HIPCHK(hipEventRecord(h->ev[1], h->st));
   const auto w1 = std::chrono::steady_clock::now();
   h->n_divided = keep;
@@ -3309,7 +3313,7 @@ int hge_split_begin(hge_engine* h) {
   }
   h->sp_active = false;  // the walk-only split: every part computes everything else
   replay_begin(h);
-  if (!h->cs_pending) {
+  if (!h->cstep) {
     h->err = "nothing staged (hge_replay_prepare first)";
     return HGE_ERR_ARG;
   }
@@ -3341,7 +3345,7 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
                       int32_t hmax, int32_t* rows_out, uint64_t* ssc_out, int32_t* nrows,
                       int32_t* natural) {
   GUARD_BEGIN
-  if (!h->cs_pending || !start || hmax < 2) return HGE_ERR_ARG;
+  if (!h->cstep || !start || hmax < 2) return HGE_ERR_ARG;
   const int N = h->N, NW = h->NW;
   h->s_hist.need((size_t)hmax * N + N);
   h->s_hssc.need((size_t)hmax * N * NW);
@@ -3359,12 +3363,11 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
   h->s_gran.need(2 * (size_t)N);
   HIPCHK(hipMemsetAsync(h->s_bar.p, 0, 8, h->st));
   HIPCHK(hipMemsetAsync(h->s_gran.p, 0, 16 * (size_t)N, h->st));
-  const int npow = N <= 64 ? 64 : N <= 128 ? 128 : 256;
-  h->s_mb.need((size_t)npow * npow);
+  h->s_mb.need((size_t)h->npow() * h->npow());
   auto lk = h->frontier_lock();  // until the walk has drained (the sync below)
   Tables t = h->tables();
-  const int32_t* olen = h->k_len;
-  const int32_t* len = h->k_len + N;
+  const int32_t* olen = h->cstep->olen;
+  const int32_t* len = h->cstep->len;
   int rlo = 0, Rprev = 0;
   const int32_t* rlo_dev = nullptr;
   uint64_t* gran = h->s_gran.p;
@@ -3377,11 +3380,8 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
   int hm = hmax, ex = std::max(0, (int)extra), nostall = 0;
   void* args[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
                   &st0, &hist, &hm, &cut, &ex, &nostall};
-  const void* fn = N <= 64 ? (const void*)k_rounds_direct<1024, 64>
-                 : N <= 128 ? (const void*)k_rounds_direct<1024, 128>
-                            : (const void*)k_rounds_direct<1024, 256>;
   h->prof_begin("k_rounds_direct_walk");
-  HIPCHK(h->launch_resident(fn, dim3(N), dim3(1024), args));
+  HIPCHK(h->launch_resident(h->direct_fn(), dim3(N), dim3(1024), args));
   h->prof_end();
   int32_t rs[2] = {0, 0}, e = 0;
   h->d2h(rs, rstate, 8);
@@ -3411,7 +3411,7 @@ int hge_frontier_rows(hge_engine* h, int32_t from, int32_t n, int32_t* rows_out,
 int hge_split_finish(hge_engine* h, const int32_t* rows, const uint64_t* ssc, int32_t nrows,
                      int32_t natural, int64_t* n_ordered) {
   GUARD_BEGIN
-  if (!h->cs_pending || !rows || nrows < 1 || (nrows > 1 && !ssc)) return HGE_ERR_ARG;
+  if (!h->cstep || !rows || nrows < 1 || (nrows > 1 && !ssc)) return HGE_ERR_ARG;
   const int N = h->N, NW = h->NW;
   h->ext_on = true;
   h->ext_natural = natural != 0;

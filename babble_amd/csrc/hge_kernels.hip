@@ -944,7 +944,7 @@ struct RoundAssign {
   // G lanes), the first witness of rounds [r_from, R) (r_from < 0: the walk's first
   // round, rlo_dev[0]; the rows below it are unchanged since the last batch), the
   // round count, overflow flag and hand-off error (0), and the lowest round over
-  // und[0, n_und) and the ids [lo, hi), final at minw[Rcap + 2]
+  // und[0, n_und) and the ids [lo, hi), final at minw's kTailMinRound word
   int32_t* minw;
   int G;
   const int32_t* und;
@@ -1041,19 +1041,19 @@ __device__ __forceinline__ void round_minw_body(const Tables& t, int r0, const i
     for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) atomicMin(&s_m, m);
     __syncthreads();
-    if (threadIdx.x == 0) minw[t.Rcap + 4 + b] = s_m;
+    if (threadIdx.x == 0) minw[t.Rcap + hge_plan::kTailPartial + b] = s_m;
     return;
   }
   const int r = r0 + bid * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  // the round count and overflow flag ride along at minw[Rcap..Rcap+1], the next
-  // batch's lowest candidate round at [Rcap+2] (INF32 here when k_min_round* lower it
-  // after this kernel) and the rounds walk's hand-off error flag at [Rcap+3]: one
-  // readback for all of them
+  // the round count and overflow flag ride along behind minw's Rcap rows (the tail
+  // words of hge_plan.h), with the next batch's lowest candidate round (INF32 here when
+  // k_min_round* lower it after this kernel) and the rounds walk's hand-off error
+  // flag: one readback for all of them
   if (bid == 0 && threadIdx.x == 0) {
-    minw[t.Rcap] = rstate[0];
-    minw[t.Rcap + 1] = rstate[1];
-    minw[t.Rcap + 2] = INF32;
-    minw[t.Rcap + 3] = err_in ? *err_in : 0;
+    minw[t.Rcap + hge_plan::kTailRounds] = rstate[0];
+    minw[t.Rcap + hge_plan::kTailOverflow] = rstate[1];
+    minw[t.Rcap + hge_plan::kTailMinRound] = INF32;
+    minw[t.Rcap + hge_plan::kTailHandoffErr] = err_in ? *err_in : 0;
   }
   if (rstate[1] || r >= rstate[0]) return;
   int m = INF32;
@@ -1145,9 +1145,9 @@ __global__ void __launch_bounds__(1024) k_rounds_walk(Tables t, const uint16_t* 
   const int R = rstate[0], ov = rstate[1];
   int32_t* minw = ra.minw;
   if (tid == 0) {
-    minw[t.Rcap] = R;
-    minw[t.Rcap + 1] = ov;
-    minw[t.Rcap + 3] = 0;
+    minw[t.Rcap + hge_plan::kTailRounds] = R;
+    minw[t.Rcap + hge_plan::kTailOverflow] = ov;
+    minw[t.Rcap + hge_plan::kTailHandoffErr] = 0;
   }
   if (!ov) {
     int r0 = ra.r_from >= 0 ? ra.r_from : *ra.rlo_dev;
@@ -1170,7 +1170,7 @@ __global__ void __launch_bounds__(1024) k_rounds_walk(Tables t, const uint16_t* 
   for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
   if (lane == 0 && m != INF32) atomicMin(&s_mr, m);
   __syncthreads();
-  if (tid == 0) minw[t.Rcap + 2] = s_mr;
+  if (tid == 0) minw[t.Rcap + hge_plan::kTailMinRound] = s_mr;
 }
 
 // ---------------------------------------------------------------------------
@@ -3261,7 +3261,7 @@ __global__ void __launch_bounds__(1024) k_consensus_call(Tables t, FameCall f, O
 
 // An online call's consensus at N <= 16 with its control built on the device
 // (k_consensus_call's stages after a prologue): the round count and the candidates'
-// lowest round are read where the rounds walk left them (rstate, minw[Rcap + 2]), so
+// lowest round are read where the rounds walk left them (rstate, minw's tail), so
 // the host enqueues the whole call without a round trip in the middle.  The single
 // call's DecideFame windows are one pair per round lcr+1 .. R-2 (consensus_batch's
 // enumeration for one call); the rounds DecideRoundReceived examines are
@@ -3285,7 +3285,7 @@ __global__ void __launch_bounds__(1024) k_consensus_dyn(Tables t, DynCall dc) {
   const int tid = threadIdx.x, T = blockDim.x, N = t.N;
   if (tid == 0) {
     const int R = dc.rstate[0];
-    const int mnr = dc.minw[dc.Rcap + 2];
+    const int mnr = dc.minw[dc.Rcap + hge_plan::kTailMinRound];
     const int rr_lo = mnr >= INF32 - 1 ? INF32 : mnr + 1;  // (INF32: no candidate)
     s_R = R;
     s_rrlo = rr_lo;

@@ -1,8 +1,10 @@
-// hge_plan.h — the host planning of one consensus batch as plain C++: R_c per call,
-// DecideFame's (round, call) windows, the control block's layout and contents, the
-// results block's layout.  No HIP, no engine state: vectors and ints in, small
-// structs out (hge_engine.hip includes it; tests/abi/hge_plan_test.cpp checks it on
-// the CPU against brute-force restatements).
+// hge_plan.h — the host planning of one batch as plain C++.  The consensus calls: R_c
+// per call, DecideFame's (round, call) windows, the control block's layout and
+// contents, the results block's layout.  The coordinate and rounds step before them:
+// its control block's layout and contents, the sweep segment list, the words of the
+// rounds readback.  No HIP, no engine state: vectors and ints in, small structs out
+// (hge_engine.hip includes it, and the kernels take the readback's constants from it;
+// tests/abi/hge_plan_test.cpp checks it on the CPU against brute-force restatements).
 #pragma once
 
 #include <algorithm>
@@ -189,6 +191,122 @@ inline Results parse_results(const ResultsLayout& L, const int32_t* ho, const in
     r.ntx += v;
   }
   return r;
+}
+
+// ---------------------------------------------------------------------------
+// The coordinate and rounds step (the half of a batch before the consensus calls)
+// ---------------------------------------------------------------------------
+
+// rstate, the first words of the step's control block: {R, overflow, new witnesses}.
+// The overflow word: 0, or why the kernels after the walk stand down
+constexpr int32_t kRoundsFull = 1;       // the rounds table is full: grow it, walk again
+constexpr int32_t kRoundsStoodDown = 4;  // the wide walk's hand-off timed out (set with the error flag)
+
+// The rounds readback rides behind the Rcap first-witness ids of the minw table, word
+// Rcap + k: one copy brings the round count and the rounds' first witnesses back
+constexpr int kTailRounds = 0;      // the round count (rstate[0])
+constexpr int kTailOverflow = 1;    // rstate's overflow word
+constexpr int kTailMinRound = 2;    // the lowest round of the next batch's candidates
+constexpr int kTailHandoffErr = 3;  // the wide walk's hand-off error flag
+constexpr int kTailPartial = 4;     // the fixed words end; k_round_tail's partial minima from here
+// the tail read back (`tail`: the words from Rcap on, `mr` partial minima folded in)
+struct RoundsTail {
+  int32_t R = 0, overflow = 0, min_round = 0, handoff_err = 0;
+};
+inline RoundsTail parse_rounds_tail(const int32_t* tail, int mr) {
+  RoundsTail r{tail[kTailRounds], tail[kTailOverflow], tail[kTailMinRound], tail[kTailHandoffErr]};
+  for (int b = 0; b < mr; b++) r.min_round = std::min(r.min_round, tail[kTailPartial + b]);
+  return r;
+}
+
+// a sweep segment: SEG positions of one chain from `pos` (the kernels read it as int2)
+struct Seg {
+  int32_t chain, pos;
+};
+inline int seg_count(int olen, int len, int SEG) { return len > olen ? (len - olen + SEG - 1) / SEG : 0; }
+// The fixed-point sweeps' segment list: every chain's new positions [olen, len) in
+// pieces of SEG, in position-major order (workgroups are dispatched roughly in index
+// order, so early positions of every chain are swept first and later segments read
+// rows already updated in this sweep: Gauss-Seidel in time order); chains keep their
+// order at equal positions.
+inline void sweep_segments(std::vector<Seg>& segs, const std::vector<int32_t>& olen, const std::vector<int32_t>& len,
+                           int SEG) {
+  segs.clear();
+  for (int c = 0; c < (int)len.size(); c++)
+    for (int k = olen[c]; k < len[c]; k += SEG) segs.push_back(Seg{c, k});
+  std::stable_sort(segs.begin(), segs.end(), [](const Seg& a, const Seg& b) { return a.pos < b.pos; });
+}
+
+// The step's control block (int32 words, one upload): rstate (4 words) | the chains'
+// old lengths, new lengths | plo (where the runs kernel starts) | qlo (where the FD
+// transpose starts: written by the device past a fresh state) | the fss rows' first
+// position per chain, their offsets, their total | the segment list (8-byte aligned)
+// | the segments' chain-major bases | a split part's candidate bounds (low, high) |
+// the one-window lastAncestors pass's risky id | an online call's packed event
+// records (16-byte aligned).  up_words = 0 means "no packed upload": the block then
+// ends at the risky id.  A packed upload is never empty (the step has new events and
+// the upload holds exactly them), which the engine checks before it asks for a layout.
+struct CoordsCtl {
+  int N = 0;
+  size_t nsegs = 0, up_words = 0;
+  size_t len = 0, plo = 0, qlo = 0, fss = 0, segs = 0, segbase = 0, cand = 0, risky = 0, up = 0, total = 0;
+  static constexpr size_t rstate = 0;
+  size_t olen() const { return len; }
+  size_t nlen() const { return len + N; }
+  size_t fss_lo() const { return fss; }
+  size_t fss_off() const { return fss + N; }
+  size_t fss_total() const { return fss + 2 * (size_t)N; }
+  size_t cand_lo() const { return cand; }
+  size_t cand_hi() const { return cand + N; }
+};
+inline CoordsCtl coords_ctl_layout(int N, size_t nsegs, size_t up_words) {
+  CoordsCtl L;
+  L.N = N;
+  L.nsegs = nsegs;
+  L.up_words = up_words;
+  L.len = 4;
+  L.plo = L.len + 2 * (size_t)N;
+  L.qlo = L.plo + N;
+  L.fss = L.qlo + N;
+  L.segs = (L.fss + 2 * (size_t)N + 1 + 1) & ~(size_t)1;
+  L.segbase = L.segs + 2 * nsegs;
+  L.cand = L.segbase + N;
+  L.risky = L.cand + 2 * (size_t)N;
+  L.up = (L.risky + 1 + 3) & ~(size_t)3;
+  L.total = up_words ? L.up + up_words : L.risky + 1;
+  return L;
+}
+
+// The block's contents for layout L (= coords_ctl_layout(N, segs.size(), ...)), the
+// upload's words left zero: rstate = {R, 0, 0}; plo = olen - 1, never below 0; the fss
+// entries of a walk from a fresh state (rows from position 0 of every chain; qlo = 0
+// too); segment bases for pieces of SEG; `cand`: a split part's N low then N high
+// bounds (empty: not a split part, zeros); the risky id -1.  Returns the fresh walk's
+// fss total (every chain's length).
+inline int fill_coords_ctl(std::vector<int32_t>& kc, const CoordsCtl& L, int R, const std::vector<int32_t>& olen,
+                           const std::vector<int32_t>& len, const std::vector<Seg>& segs, int SEG,
+                           const std::vector<int32_t>& cand) {
+  const int N = L.N;
+  kc.assign(L.total, 0);
+  kc[CoordsCtl::rstate] = R;
+  int tot = 0;
+  for (int c = 0, b = 0; c < N; c++) {
+    kc[L.olen() + c] = olen[c];
+    kc[L.nlen() + c] = len[c];
+    kc[L.plo + c] = std::max(olen[c] - 1, 0);
+    kc[L.fss_off() + c] = tot;
+    tot += len[c];
+    kc[L.segbase + c] = b;
+    b += seg_count(olen[c], len[c], SEG);
+    if (!cand.empty()) {
+      kc[L.cand_lo() + c] = cand[c];
+      kc[L.cand_hi() + c] = cand[N + c];
+    }
+  }
+  kc[L.fss_total()] = tot;
+  if (!segs.empty()) memcpy(&kc[L.segs], segs.data(), sizeof(Seg) * segs.size());
+  kc[L.risky] = -1;
+  return tot;
 }
 
 }  // namespace hge_plan

@@ -1,5 +1,6 @@
-// The consensus batch's host planning (babble_amd/csrc/hge_plan.h) against brute-force
-// restatements: linear scans, no bisection, no merge pass.  Host only, links nothing
+// The host planning of a batch (babble_amd/csrc/hge_plan.h: the consensus calls'
+// windows and blocks, the coordinate step's control block) against brute-force
+// restatements: linear scans, no bisection, no merge pass, no sort.  Host only, links nothing
 // of the engine (tests/test_plan.py runs it).  Prints "ok <checks>".
 #include <cstdio>
 #include <cstdlib>
@@ -146,9 +147,151 @@ static void check_results_layout(int ncalls, int ncand, bool ord) {
         ResultsLayout::kLcr == 3 && ResultsLayout::kTx == 4 && ResultsLayout::kCounts == 8);
 }
 
+// ---- the coordinate step's control block
+// the arithmetic the layout replaces, as the engine used to write it inline
+static void check_coords_layout(int N, size_t nsegs, size_t up_words) {
+  const CoordsCtl L = coords_ctl_layout(N, nsegs, up_words);
+  const size_t n = (size_t)N;
+  const size_t o_len = 4, o_plo = o_len + 2 * n, o_qlo = o_plo + n, o_lo = o_qlo + n;
+  const size_t o_seg = (o_lo + 2 * n + 1 + 1) & ~(size_t)1;
+  const size_t o_sb = o_seg + 2 * nsegs, o_fd = o_sb + n, size = o_fd + 2 * n + 1;
+  const size_t o_up = (size + 3) & ~(size_t)3;
+  CHECK(CoordsCtl::rstate == 0);
+  CHECK(L.olen() == o_len && L.nlen() == o_len + n);
+  CHECK(L.plo == o_plo && L.qlo == o_qlo);
+  CHECK(L.fss_lo() == o_lo && L.fss_off() == o_lo + n && L.fss_total() == o_lo + 2 * n);
+  CHECK(L.segs == o_seg && L.segbase == o_sb);
+  CHECK(L.cand_lo() == o_fd && L.cand_hi() == o_fd + n && L.risky == o_fd + 2 * n);
+  CHECK(L.up == o_up);
+  CHECK(L.total == (up_words ? o_up + up_words : size));
+  // regions (start, words) in order, disjoint, inside the total
+  const size_t reg[][2] = {{CoordsCtl::rstate, 3}, {L.olen(), n},    {L.nlen(), n},    {L.plo, n},
+                           {L.qlo, n},             {L.fss_lo(), n},  {L.fss_off(), n}, {L.fss_total(), 1},
+                           {L.segs, 2 * nsegs},    {L.segbase, n},   {L.cand_lo(), n}, {L.cand_hi(), n},
+                           {L.risky, 1},           {L.up, up_words}};
+  size_t end = 0;
+  for (const auto& r : reg) {
+    if (r[1] == 0) continue;
+    CHECK(r[0] >= end);
+    end = r[0] + r[1];
+  }
+  CHECK(end <= L.total);
+  CHECK(L.segs % 2 == 0);  // int2 entries
+  CHECK(L.up % 4 == 0);    // 16-byte aligned records
+}
+// position-major, chains ascending at equal positions: a naive double loop
+static std::vector<Seg> naive_segments(const V32& olen, const V32& len, int SEG) {
+  std::vector<Seg> out;
+  int maxlen = 0;
+  for (int32_t l : len) maxlen = std::max(maxlen, (int)l);
+  for (int p = 0; p < maxlen; p++)
+    for (int c = 0; c < (int)len.size(); c++)
+      if (p >= olen[c] && p < len[c] && (p - olen[c]) % SEG == 0) out.push_back(Seg{c, p});
+  return out;
+}
+static void check_segments(const V32& olen, const V32& len, int SEG) {
+  std::vector<Seg> segs(3, Seg{-1, -1});  // (cleared by the call)
+  sweep_segments(segs, olen, len, SEG);
+  const std::vector<Seg> ref = naive_segments(olen, len, SEG);
+  CHECK(segs.size() == ref.size());
+  for (size_t i = 0; i < segs.size() && i < ref.size(); i++)
+    CHECK(segs[i].chain == ref[i].chain && segs[i].pos == ref[i].pos);
+  int total = 0;
+  for (size_t c = 0; c < len.size(); c++) total += seg_count(olen[c], len[c], SEG);
+  CHECK((size_t)total == ref.size());
+}
+static void check_coords_fill(int R, const V32& olen, const V32& len, int SEG, bool with_segs, bool split,
+                              size_t up_words) {
+  const int N = (int)len.size();
+  std::vector<Seg> segs;
+  if (with_segs) sweep_segments(segs, olen, len, SEG);
+  V32 clo(N), chi(N), cand;
+  for (int c = 0; c < N; c++) {
+    clo[c] = 1000 + 3 * c;
+    chi[c] = 5000 + 7 * c;
+  }
+  if (split) {
+    cand = clo;
+    cand.insert(cand.end(), chi.begin(), chi.end());
+  }
+  const CoordsCtl L = coords_ctl_layout(N, segs.size(), up_words);
+  V32 kc(5, 77);
+  const int tot = fill_coords_ctl(kc, L, R, olen, len, segs, SEG, cand);
+  CHECK(kc.size() == L.total);
+  if (kc.size() != L.total) return;
+  // the naive fill: every word of the block from its definition, zero elsewhere
+  V32 ref(L.total, 0);
+  ref[0] = R;
+  int64_t sum = 0;
+  for (int c = 0; c < N; c++) {
+    ref[4 + c] = olen[c];
+    ref[4 + N + c] = len[c];
+    ref[4 + 2 * N + c] = olen[c] > 0 ? olen[c] - 1 : 0;
+    // (qlo: zero as uploaded) the fss rows of a fresh walk: from position 0, chain after chain
+    ref[4 + 4 * N + c] = 0;
+    ref[4 + 5 * N + c] = (int32_t)sum;
+    sum += len[c];
+    int before = 0;  // segments of the chains below c
+    for (int d = 0; d < c; d++)
+      for (int k = olen[d]; k < len[d]; k += SEG) before++;
+    ref[L.segbase + c] = before;
+    if (split) {
+      ref[L.cand_lo() + c] = clo[c];
+      ref[L.cand_hi() + c] = chi[c];
+    }
+  }
+  ref[4 + 6 * N] = (int32_t)sum;
+  for (size_t i = 0; i < segs.size(); i++) {
+    ref[L.segs + 2 * i] = segs[i].chain;
+    ref[L.segs + 2 * i + 1] = segs[i].pos;
+  }
+  ref[L.risky] = -1;
+  CHECK(tot == (int)sum);
+  CHECK(kc == ref);
+  // with segments, base[c] is where chain c's segment k sits once the list is chain-major
+  if (with_segs) {
+    std::vector<Seg> cm = segs;
+    std::stable_sort(cm.begin(), cm.end(), [](const Seg& a, const Seg& b) { return a.chain < b.chain; });
+    for (size_t i = 0; i < cm.size(); i++)
+      CHECK((int)i == kc[L.segbase + cm[i].chain] + (cm[i].pos - olen[cm[i].chain]) / SEG);
+  }
+}
+
 int main() {
   std::mt19937_64 rng(12345);
   auto rnd = [&](int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); };
+
+  // ---------------- the coordinate step: layout, segment list, contents
+  static_assert(kTailRounds == 0 && kTailOverflow == 1 && kTailMinRound == 2 && kTailHandoffErr == 3 &&
+                    kTailPartial == 4,
+                "the rounds tail: four fixed words, then the partial minima");
+  static_assert(kRoundsFull == 1 && kRoundsStoodDown == 4, "rstate's overflow codes");
+  static_assert(sizeof(Seg) == 8, "two int32 (the kernels' int2)");
+  {
+    const int32_t tail[7] = {41, 0, 17, 1, 19, 12, 30};
+    const RoundsTail a = parse_rounds_tail(tail, 0), b = parse_rounds_tail(tail, 3);
+    CHECK(a.R == 41 && a.overflow == 0 && a.min_round == 17 && a.handoff_err == 1);
+    CHECK(b.R == 41 && b.min_round == 12);  // the partial minima folded in
+  }
+  for (int N = 1; N <= 300; N++)
+    for (int segs = 0; segs < 2; segs++)
+      for (int up = 0; up < 2; up++)
+        check_coords_layout(N, segs ? (size_t)rnd(1, 5000) : 0, up ? (size_t)rnd(1, 400) * 14 : 0);
+  check_coords_layout(256, 156250, 0);  // a 256/10M replay's segments
+  for (int it = 0; it < 600; it++) {
+    const int N = it < 300 ? it + 1 : rnd(1, 300);
+    const int SEG = it % 2 ? 16 : 64;
+    V32 olen(N), len(N);
+    for (int c = 0; c < N; c++) {
+      olen[c] = it % 3 == 0 ? 0 : rnd(0, 300);                   // a fresh state | mid-stream
+      len[c] = olen[c] + (rnd(0, 3) == 0 ? 0 : rnd(0, 5 * SEG));  // some chains without a new event
+    }
+    check_segments(olen, len, SEG);
+    check_coords_fill(rnd(0, 1000), olen, len, SEG, it % 4 != 1, it % 5 == 0, it % 2 ? (size_t)rnd(1, 64) * 14 : 0);
+  }
+  check_segments({0, 0}, {0, 0}, 16);  // nothing new
+  check_segments({5}, {6}, 64);        // one event
+  check_segments({0, 63, 64, 65}, {128, 128, 128, 128}, 64);
 
   // ---------------- rounds_at_calls
   {

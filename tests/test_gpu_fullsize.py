@@ -66,3 +66,29 @@ def test_full_size(n, E):
     finally:
         eng.close()
 
+
+def test_long_chain_n2():
+    """Two participants, 140,000 events (seed 5: chains of 70,056 and 69,944), four
+    calls: at N <= 32 a chain of 65,535 events or more takes the walk over int32
+    first-strong-seer rows (k_fss's int32 rows, k_rounds_fss), which no other test
+    reaches.  Checked against the oracle's whole-stream digests (34,887 rounds,
+    139,977 events ordered) and the size-independent properties."""
+    from babble_amd.engine import Engine, events_array
+    n, E, K, seed = 2, 140_000, 35_000, 5
+    dag = random_gossip(n, E, seed=seed)
+    calls = schedule(E, K)
+    gf = json.load(open(os.path.join(ROOT, "tests", "golden", f"bench_n{n}_e{E}_k{K}_s{seed}_full.json")))
+    eng = Engine(n, E)
+    try:
+        st, order, counts = eng.replay(events_array(dag), calls)
+        assert (st >= 0).all()
+        assert len(order) == gf["ordered"]
+        rounds, wit = eng.event_rounds()
+        rr, cts = eng.event_received()
+        check_run(dag, st, order, counts, rounds, wit, rr, cts)
+        from digest import compare_full, engine_state
+        bad = compare_full(engine_state(eng, st, order, counts), gf)
+        assert not bad, f"fields differing from the oracle's whole-stream digests: {bad}"
+    finally:
+        eng.close()
+

@@ -38,6 +38,9 @@ CASES = [
     (32, 4000, 32, 16, 10, 0.05, 0.5),
     (33, 3000, 50, 17, 0, 0.0, 0.0),
     (64, 6000, 64, 18, 0, 0.0, 0.0),
+    # two participants, a round every ~4 events: the start of the long-chain stream whose
+    # whole-stream golden (bench_n2_e140000_k35000_s5_full.json) the scale mode made
+    (2, 3000, 750, 5, 0, 0.0, 0.0),
 ]
 
 

@@ -1,6 +1,7 @@
 """The consensus batch's host planning (babble_amd/csrc/hge_plan.h): R_c per call,
 DecideFame's windows, the control block's layout and contents, the results block's
-layout -- against brute-force restatements (tests/abi/hge_plan_test.cpp).  Plain
+layout, and the coordinate step's control block (layout, sweep segment list,
+contents) -- against brute-force restatements (tests/abi/hge_plan_test.cpp).  Plain
 host C++, no engine and no device: this runs in the CPU suite."""
 import os
 import subprocess
