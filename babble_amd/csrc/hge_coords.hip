@@ -662,6 +662,49 @@ __global__ void __launch_bounds__(256) k_fd_transpose_ts(Tables t, const FT* FDT
   }
 }
 
+// k_fd_transpose_ts<uint16_t> without the timestamps: FDT[j][c][q] -> the packed FD16
+// rows alone (no tsch gather, no FDTD / FDTW).  A fresh bulk replay whose median reads
+// the FD rows itself (k_median_rows) takes it; the timestamp table is then stale until
+// k_fd_transpose_ts runs over the positions a later reader needs (hge_engine.hip,
+// ensure_fdtd).  Same tile order, 8-byte run loads and streaming stores.
+__global__ void __launch_bounds__(256) k_fd_rows16(Tables t, const uint16_t* FDT, const int32_t* plo,
+                                                   const int32_t* len) {
+  __shared__ uint16_t tile[64][66];  // [chain j][position]: rows an odd number of words apart
+  const int N = t.N;
+  const size_t ccap = t.ccap;
+  const int64_t nbk = (int64_t)gridDim.x * gridDim.y * gridDim.z;
+  const int64_t lb = xcd_block(blockIdx.x + (int64_t)gridDim.x * (blockIdx.y + (int64_t)gridDim.y * blockIdx.z), nbk);
+  const int bx = (int)(lb % gridDim.x), by = (int)((lb / gridDim.x) % gridDim.y), bz = (int)(lb / ((int64_t)gridDim.x * gridDim.y));
+  const int a = bx;  // source chain c
+  const int pend = len[a];
+  const int c0 = by * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 64 x 4
+  const int pb = plo[a] & ~3;  // (tiles start at a multiple of 4 positions: one 8-byte load per lane)
+  const int qd = threadIdx.x & 15, r0 = threadIdx.x >> 4;
+  for (int p0 = pb + bz * 64; p0 < pend; p0 += gridDim.z * 64) {
+    // read phase: thread i takes row jj = c0 + (i >> 4) + 16 h, positions p0 + 4 (i & 15) .. + 3
+    uint2 w[4];
+#pragma unroll
+    for (int h = 0; h < 4; h++) {
+      const int jj = c0 + r0 + 16 * h, q = p0 + 4 * qd;
+      w[h] = (jj < N && q < pend) ? *(const uint2*)(FDT + ((size_t)jj * N + a) * ccap + q) : make_uint2(~0u, ~0u);
+    }
+#pragma unroll
+    for (int h = 0; h < 4; h++) {
+      const uint32_t u[4] = {w[h].x & 0xFFFFu, w[h].x >> 16, w[h].y & 0xFFFFu, w[h].y >> 16};
+#pragma unroll
+      for (int e = 0; e < 4; e++)  // the packed row value: FD + 1, 0xFFFF = none (positions past the chain: none)
+        tile[r0 + 16 * h][4 * qd + e] = (u[e] == 0xFFFFu || p0 + 4 * qd + e >= pend) ? (uint16_t)0xFFFFu : (uint16_t)(u[e] + 1);
+    }
+    __syncthreads();
+    for (int r = ty; r < 64; r += 4) {  // wave ty writes rows r: the 64 columns of one row each time
+      const int q = p0 + r, jj = c0 + tx;
+      if (q < pend && jj < N) __builtin_nontemporal_store(tile[tx][r], t.FD16 + rowoff(t, a, q) + jj);
+    }
+    __syncthreads();
+  }
+}
+
 // the uint16 tables widened to int32 at the switch to int32 positions: runs
 // (0xFFFF -> INF32, else the value) and FD rows (0xFFFF -> INF32, else value - 1)
 __global__ void k_fdt16_to32(const uint16_t* src, int32_t* dst, size_t n, int bias) {

@@ -27,6 +27,7 @@
 #include "../../include/hge.h"
 #include "hge_plan.h"
 #include "hge_kernels.hip"
+#include "hge_median_rows.hip"
 #include "hge_wide32.hip"
 #include "hge_coords.hip"
 #include "hge_coords_win.hip"
@@ -252,6 +253,18 @@ struct hge_engine {
   }
   DBuf<int32_t> d_FDTD;  // N > 16: timestamp offsets at the FD positions (the wide median)
   DBuf<uint8_t> d_FDTW;  // N > 16: per (row, 64-column tile) out-of-range flags of d_FDTD
+  // A fresh bulk replay at uint16 positions writes the FD rows alone (k_fd_rows16) and
+  // takes its median from them (k_median_rows): d_FDTD / d_FDTW then hold no row of the
+  // current coordinates (fdtd_stale) until k_fd_transpose_ts has run over the positions a
+  // reader needs.  Every reader of the two tables calls ensure_fdtd() first; the replay
+  // itself ends with that pass over the still-undetermined events' rows (fdtd_tail).
+  bool rows_bulk = false;   // hge_replay_run: this replay's coordinate step may skip the timestamps
+  bool fdtd_stale = false;
+  int fdtd_maxlen = 0;      // the longest chain of the stale coordinates
+  DBuf<int32_t> s_fdlo;     // [2N]: the first position to refresh per chain, then the chains' lengths
+  // test hook (HGE_TEST_MEDIAN_ROWS_FALLBACK=1): the coordinate step skips the timestamps
+  // but the median takes k_median_wave, so ensure_fdtd()'s full pass runs
+  bool test_rows_fallback = getenv("HGE_TEST_MEDIAN_ROWS_FALLBACK") != nullptr;
   DBuf<int32_t> d_WLA;   // N > 16: round frontier rows transposed (k_witness_la)
   DBuf<uint16_t> d_WLR;  // N > 64, packed path: the same rows row-major as LA + 1 (theta)
   DBuf<uint64_t> d_ssc, s_gran;
@@ -437,7 +450,7 @@ struct hge_engine {
                              &s_und2,    &s_part,   &s_fst,    &d_FSS,
                              &d_FDT,     &s_chg,    &s_bar,   &s_bseg,   &s_kctl,    &s_cctl,
                              &s_out,     &s_hn,     &s_hres,  &s_dirty,  &d_WLA,     &s_lwpos,
-                             &s_lwrisky, &s_src,    &s_relay, &s_rfail};
+                             &s_lwrisky, &s_src,    &s_relay, &s_rfail,  &s_fdlo};
     for (auto* b : i32s) b->free_();
     s_dec2.free_();
     s_lwplan.free_();
@@ -914,6 +927,9 @@ struct hge_engine {
     bool frontier_started = false;  // k_frontier_start's block (k_chain_fill_qlo, k_la_seq)
     bool qlo_done = false;          // k_fd_qlo's blocks (the same two)
     bool fd_done = false;           // the FD rows and FDT runs (k_la_seq, N <= 16)
+    // the FD rows without their timestamp offsets (k_fd_rows16): a fresh bulk replay whose
+    // median reads the rows itself (k_median_rows)
+    bool fd_rows_only = false;
     bool take_frontier_start() { return std::exchange(frontier_started, false); }  // (a later attempt starts again)
   };
   std::optional<CoordStep> cstep;
@@ -1063,6 +1079,7 @@ struct hge_engine {
       s.maxlen = std::max(s.maxlen, chain_len[c]);
       s.minlen = std::min(s.minlen, chain_len[c]);
     }
+    s.fd_rows_only = rows_bulk && s.fresh && s.n0 == 0 && fdt16() && !split_on() && !rec_on && !ext_on;
     std::vector<int32_t> cand;
     if (split_on()) {
       // FD timestamp rows (the median's input) of the ids [cand_lo, the part's end)
@@ -1642,6 +1659,7 @@ struct hge_engine {
         throw EngineError(HGE_ERR_DEVICE, "test: to_wide32 stopped after stage " + std::to_string(stage));
       }
     };
+    ensure_fdtd();  // (the pass reads the uint16 runs)
     if (!(w32_done & 4)) {
       grow_chain_table(d_LA, ccap, false);
       w32_done |= 4;
@@ -1885,9 +1903,27 @@ struct hge_engine {
       }
     }
   }
+  // k_fd_transpose_ts over the stale rows of d_FDTD / d_FDTW from s_fdlo[c] on (the FD
+  // rows it writes again hold the same values); zgrid: position tiles per chain in the
+  // grid (the kernel loops past it)
+  void fdtd_pass(const char* name, int zgrid) {
+    const Tables t = tables();
+    KLAUNCH_AS(name, (k_fd_transpose_ts<uint16_t>), dim3(N, div_up(N, 64), std::max(1, std::min(zgrid, 65535))),
+               dim3(256), 0, st, t, (const uint16_t*)d_FDT.p, (const int32_t*)s_fdlo.p,
+               (const int32_t*)(s_fdlo.p + N), (const int32_t*)nullptr, (const int32_t*)nullptr);
+  }
+  // every reader of d_FDTD / d_FDTW: the whole table, when a bulk replay left it stale
+  void ensure_fdtd() {
+    if (!fdtd_stale) return;
+    if (!fdt16()) throw EngineError(HGE_ERR_INTERNAL, "stale FD timestamp rows past the uint16 runs");
+    HIPCHK(hipMemsetAsync(s_fdlo.p, 0, 4 * (size_t)N, st));
+    fdtd_pass("fdtd_ensure (k_fd_transpose_ts<uint16_t>)", div_up(std::max(fdtd_maxlen, 1), 64));
+    fdtd_stale = false;
+  }
   // firstDescendants: the FDT runs from the LA rows, then FDT -> FD rows
   void first_descendants(const Tables& t, const CoordStep& s) {
     if (s.fd_done) return;  // (k_la_seq wrote the FD rows and FDT runs)
+    if (!s.fresh) ensure_fdtd();  // (the stale rows' runs and lengths are the old ones)
     const int32_t* olen = s.olen;
     const int32_t* len = s.len;
     const int maxnew = s.maxnew;
@@ -1917,7 +1953,16 @@ struct hge_engine {
       span = std::max(span, s.maxlen);
     }
     // (a split part writes the timestamp rows of its own candidates only)
-    if (fdt16())
+    if (s.fresh) fdtd_stale = false;  // (every row is written again below, or marked)
+    if (s.fd_rows_only) {
+      // the FD rows alone: the timestamp table is stale from position 0 of every chain
+      KLAUNCH(k_fd_rows16, dim3(N, div_up(N, 64), std::min(div_up(span, 64), 65535)), dim3(256), 0, st, t,
+              (const uint16_t*)d_FDT.p, (const int32_t*)s.qlo, len);
+      s_fdlo.need(2 * (size_t)N);
+      h2d(s_fdlo.p + N, chain_len.data(), 4 * (size_t)N);
+      fdtd_maxlen = s.maxlen;
+      fdtd_stale = true;
+    } else if (fdt16())
       KLAUNCH((k_fd_transpose_ts<uint16_t>), dim3(N, div_up(N, 64), std::min(div_up(span, 64), 65535)), dim3(256),
               0, st, t, (const uint16_t*)d_FDT.p, s.qlo, len, (const int32_t*)s.cand_lo,
               (const int32_t*)s.cand_hi);
@@ -2032,6 +2077,7 @@ struct hge_engine {
       b.got_order = false;
       b.split_done = true;
     }
+    fdtd_tail(b);
     tp[3] = now_ns();
     close_batch(b);
     tp[4] = now_ns();
@@ -2802,6 +2848,25 @@ struct hge_engine {
             c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, s_clast.p, s_dec.p);
   }
 
+  // the end of a bulk replay that took its median from the FD rows: the rows of the
+  // still-undetermined events (a later online call's k_median_wave reads them), from the
+  // lowest such position of every chain.  The new undetermined list and its count are on
+  // the device (bucket_and_sort): no round trip.
+  void fdtd_tail(const Batch& b) {
+    if (!fdtd_stale) return;
+    if (!b.got_order || b.spl || !b.commit) {  // (no new list on the device: all of it)
+      ensure_fdtd();
+      return;
+    }
+    HIPCHK(hipMemcpyAsync(s_fdlo.p, s_fdlo.p + N, 4 * (size_t)N, hipMemcpyDeviceToDevice, st));
+    KLAUNCH(k_und_low, dim3(std::max(1, std::min(div_up(b.ncand, 256), 1024))), dim3(256), 0, st,
+            (const int32_t*)d_creator.p, (const int32_t*)d_index.p, (const int32_t*)d_und.p,
+            (const int32_t*)out_word(hge_plan::ResultsLayout::kUndetermined), s_fdlo.p);
+    // (mostly a tile or two per chain; the kernel loops where more is left)
+    fdtd_pass("fdtd_tail (k_fd_transpose_ts<uint16_t>)", std::min(div_up(std::max(fdtd_maxlen, 1), 64), 4));
+    fdtd_stale = false;
+  }
+
   // round received per candidate and its consensus timestamp.  N > 16: the median is a
   // wave-wide radix select (k_median_wave) over coalesced rows: the round frontier rows
   // transposed (WLA, ensure_wla, for every round a candidate can receive) and the FD
@@ -2821,9 +2886,19 @@ struct hge_engine {
                vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p, b.ncalls, 0, b.rr_lo, b.R_last,
                segoff_p, s_segcnt.p, s_segcall.p, s_segdec.p, s_segfws.p, s_theta.p, s_recv.p, s_rr.p, s_cts.p,
                bseg);
-    if (wmed)
+    if (wmed && ident && fdtd_stale && !test_rows_fallback) {
+      // a bulk replay whose coordinate step skipped the timestamps: the median from the FD rows
+      // (16 positions x 512 threads measured fastest of seven shapes)
+      constexpr int TQ = 16, NT = 512;
+      const int64_t nb = (int64_t)N * div_up(fdtd_maxlen, TQ);
+      KLAUNCH_AS("k_median_rows<16, 512>", (k_median_rows<TQ, NT>), dim3((unsigned)nb), dim3(NT),
+                 sizeof(int32_t) * TQ * (N + 4), st, t, (const int32_t*)(s_fdlo.p + N), (const int32_t*)s_recv.p,
+                 (const int32_t*)s_rr.p, (const int32_t*)bseg, (const uint64_t*)s_segfws.p, s_cts.p);
+    } else if (wmed) {
+      ensure_fdtd();
       KLAUNCH_NW(NW, NW_T, k_median_wave, dim3(div_up(b.ncand, 4 * MED_EPW)), dim3(256), 0, st, t,
                  ident ? (const int32_t*)nullptr : b.cand, b.ncand, s_recv.p, s_rr.p, bseg, s_segfws.p, s_cts.p);
+    }
   }
 
   // DivideRounds: everything inserted becomes visible to the consensus calls
@@ -3212,7 +3287,13 @@ int hge_replay_run(hge_engine* h, int64_t* n_ordered) {
   REFUSE_IF_FAILED(h)
   h->sp_active = false;
   if (h->rec_on) h->rec_dec.clear();
+  struct Bulk {  // the coordinate step of this replay alone
+    hge_engine* h;
+    ~Bulk() { h->rows_bulk = false; }
+  } bulk{h};
+  h->rows_bulk = true;
   replay_begin(h);
+  h->rows_bulk = false;
   replay_end(h, n_ordered);
   if (h->rec_on) {  // hge_split_emulate: the rest of the record
     const int64_t E = h->n_events;
