@@ -490,6 +490,7 @@ struct hge_engine {
     s_cM.free_();
     s_cn.free_();
     s_mb.free_();
+    s_wpaths.free_();
     s_hist.free_();
     s_hstate.free_();
     s_hssc.free_();
@@ -1604,16 +1605,18 @@ struct hge_engine {
     uint64_t* ssc = d_ssc.p;
     uint64_t* dbg = dbg_p();
     if (direct_rounds()) {
-      s_mb.need((size_t)npow() * npow());  // two parity blocks of npow rows x npow/2 packed words
-      uint32_t* mb = s_mb.p;
+      uint32_t* mb = walk_mb();
+      unsigned long long* paths = walk_paths();
+      unsigned long long* paths_next = s_wpaths.p + 2 * ((walk_seq + 1) & 1);
       const int32_t* nostart = nullptr;
       int32_t* nohist = nullptr;
       int hmax = 0, extra = 0;
       // tests: the walk stalls at this hand-off epoch (chain 0 never publishes it)
       const char* hs = getenv("HGE_TEST_HANDOFF_STALL");
       int stall_ep = hs ? atoi(hs) : 0;
+      int force_exact = walk_force_exact();
       void* dargs[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
-                       &nostart, &nohist, &hmax, &nostart, &extra, &stall_ep};
+                       &nostart, &nohist, &hmax, &nostart, &extra, &stall_ep, &force_exact, &paths, &paths_next};
       prof_begin("k_rounds_direct");
       HIPCHK(launch_resident(direct_fn(), dim3(N), dim3(1024), dargs));
       prof_end();
@@ -1628,6 +1631,30 @@ struct hge_engine {
       h2d(err, &one, 4);
       h2d(rstate + 1, &down, 4);
     }
+  }
+  // the direct walk's staged member rows: two parity blocks of npow rows x npow/2 packed words
+  uint32_t* walk_mb() {
+    s_mb.need((size_t)npow() * npow());
+    return s_mb.p;
+  }
+  // The walk's select-path counters (hge_walk_select_paths): two slots of {narrow, exact},
+  // cleared once here.  Walk k adds to slot k & 1 and clears the other slot as it ends,
+  // for the walk after it on the stream: no clearing launch per walk (an online call is a
+  // few hundred microseconds, a memset node was ~10 of them).
+  DBuf<unsigned long long> s_wpaths;
+  int walk_seq = 0;
+  unsigned long long* walk_paths() {
+    if (!s_wpaths.p) {
+      s_wpaths.need(4);
+      HIPCHK(hipMemset(s_wpaths.p, 0, 4 * sizeof(unsigned long long)));
+    }
+    walk_seq++;
+    return s_wpaths.p + 2 * (walk_seq & 1);
+  }
+  // tests (HGE_TEST_DIR_EXACT=1): every round of the walk takes the 16-bit select
+  static int walk_force_exact() {
+    const char* e = getenv("HGE_TEST_DIR_EXACT");
+    return e && atoi(e) != 0 ? 1 : 0;
   }
   const void* direct_fn() const {
     return N <= 64 ? (const void*)k_rounds_direct<1024, 64>
@@ -3444,7 +3471,6 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
   h->s_gran.need(2 * (size_t)N);
   HIPCHK(hipMemsetAsync(h->s_bar.p, 0, 8, h->st));
   HIPCHK(hipMemsetAsync(h->s_gran.p, 0, 16 * (size_t)N, h->st));
-  h->s_mb.need((size_t)h->npow() * h->npow());
   auto lk = h->frontier_lock();  // until the walk has drained (the sync below)
   Tables t = h->tables();
   const int32_t* olen = h->cstep->olen;
@@ -3454,13 +3480,15 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
   uint64_t* gran = h->s_gran.p;
   int32_t* err = h->s_bar.p + 1;
   uint64_t* ssc = h->s_hssc.p;
-  uint32_t* mb = h->s_mb.p;
+  uint32_t* mb = h->walk_mb();
+  unsigned long long* paths = h->walk_paths();
+  unsigned long long* paths_next = h->s_wpaths.p + 2 * ((h->walk_seq + 1) & 1);
   uint64_t* dbg = nullptr;
   const int32_t* st0 = h->s_hstate.p;
   int32_t* hist = h->s_hist.p;
-  int hm = hmax, ex = std::max(0, (int)extra), nostall = 0;
+  int hm = hmax, ex = std::max(0, (int)extra), nostall = 0, force_exact = hge_engine::walk_force_exact();
   void* args[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
-                  &st0, &hist, &hm, &cut, &ex, &nostall};
+                  &st0, &hist, &hm, &cut, &ex, &nostall, &force_exact, &paths, &paths_next};
   h->prof_begin("k_rounds_direct_walk");
   HIPCHK(h->launch_resident(h->direct_fn(), dim3(N), dim3(1024), args));
   h->prof_end();
@@ -4018,6 +4046,19 @@ int hge_kernel_stats(hge_engine* h, int k, char* name, int namecap, double* tota
 }
 
 int32_t hge_coordinate_sweeps(hge_engine* h) { return h ? h->n_sweeps : -1; }
+
+int hge_walk_select_paths(hge_engine* h, int64_t* narrow, int64_t* exact) {
+  GUARD_BEGIN
+  unsigned long long v[2] = {0, 0};
+  if (h->s_wpaths.p && h->walk_seq > 0) {
+    h->d2h(v, h->s_wpaths.p + 2 * (h->walk_seq & 1), 16);
+    h->sync();
+  }
+  if (narrow) *narrow = (int64_t)v[0];
+  if (exact) *exact = (int64_t)v[1];
+  return HGE_OK;
+  GUARD_END(h)
+}
 
 int64_t hge_host_syncs(hge_engine* h) { return h ? h->n_syncs : -1; }
 

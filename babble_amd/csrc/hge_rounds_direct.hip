@@ -33,6 +33,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hge_narrow.h"
+
+// Widths whose select runs over the 8-bit frontier-relative rows (hge_narrow.h): a
+// width built with 0 keeps the 16-bit select of every round (DESIGN.md §4.2 says which
+// widths ended where, and why).
+#ifndef HGE_DIR_NARROW_64
+#define HGE_DIR_NARROW_64 1
+#endif
+#ifndef HGE_DIR_NARROW_128
+#define HGE_DIR_NARROW_128 1
+#endif
+#ifndef HGE_DIR_NARROW_256
+#define HGE_DIR_NARROW_256 1
+#endif
+
 namespace hge {
 
 // section stamps (HGE_STAMPS) are compiled in only with -DHGE_DIR_STAMPS: the
@@ -60,7 +75,26 @@ struct DirGeo {
   static constexpr int PREF = (DIR_CH * NPOW / 4 + BS - 1) / BS;  // int4 per thread and chunk
   static constexpr int MBW = NPOW / 2;        // staged member row: packed words
   static constexpr int MVW = (CW % 4 == 0) ? 4 : 2;  // MB words per thread chunk (16 / 8 bytes)
+  // the narrow copy (hge_narrow.h): the first H window rows, four columns per word
+  static constexpr bool NARROW = NPOW <= 64 ? HGE_DIR_NARROW_64 != 0
+                               : NPOW <= 128 ? HGE_DIR_NARROW_128 != 0 : HGE_DIR_NARROW_256 != 0;
+  static constexpr int H = W / 2;             // rows the per-member bisection covers
+  static constexpr int NCW = CW / 2;          // narrow words per thread
+  static constexpr int NVW = (NCW % 4 == 0) ? 4 : (NCW % 2 == 0) ? 2 : 1;  // words per LDS read
+  static constexpr int NPS = NCW + NVW;       // LDS words per (row, part), padded like PS
+  static constexpr int NRS = TPM * NPS;       // LDS words per narrow row
+  static constexpr int NENC = (H * NPOW / 4 + BS - 1) / BS;  // narrow words a thread re-encodes per round
 };
+
+// threadIdx.x, opaque to the optimiser: what a section of the round loop derives from it
+// (row and column of a fetch slot, LDS and table addresses) is then formed in that
+// section, and not held in registers across the whole loop.  The <1024, 256> kernel
+// sits at the 128 VGPRs of 16 waves per CU; held addresses were what spilled.
+__device__ __forceinline__ int dir_tid() {
+  int x = threadIdx.x;
+  asm volatile("" : "+v"(x));
+  return x;
+}
 
 template <int BS, int NPOW>
 struct DirLDS {
@@ -70,6 +104,11 @@ struct DirLDS {
   int sCntW[DIR_MAXP][BS / 64] __attribute__((aligned(16)));  // per-wave passing members of a probe
   int sHist[DirGeo<BS, NPOW>::W / 2];  // members by first passing offset (dir_select_pm)
   uint32_t sBits[8];
+  // the narrow select's copy: the frontier positions as packed uint16 bases, laid out
+  // like one ring row (part * PS + word), and rows [lo, lo + H) of the ring re-encoded
+  uint32_t sB16[DirGeo<BS, NPOW>::NARROW ? DirGeo<BS, NPOW>::RS : 4] __attribute__((aligned(16)));
+  uint32_t sN[DirGeo<BS, NPOW>::NARROW ? DirGeo<BS, NPOW>::H * DirGeo<BS, NPOW>::NRS : 4] __attribute__((aligned(16)));
+  int sEx[2];            // per round parity: nonzero = the narrow form is not exact this round
   int sFlag[2];          // per round parity: 1 = some member exists, 2 = some chain below stopcut, 4 = hand-off failed
   int s_stamp;          // HGE_STAMPS: thread 0 accumulates probe phases into sdbg
   uint64_t sdbg[2];     // [0] count (LDS reads + VALU), [1] reduce + barrier + read
@@ -104,9 +143,10 @@ __device__ __forceinline__ void dir_fetch(const Tables& t, int c, int p0, int nr
   // unconditional loads (rows past `have` re-read the last fetched row; dir_store
   // drops them): no value select behind each load, so all of them stay in flight
   const int qmax = have * N / 4 - 1;
+  const int tx = dir_tid();
 #pragma unroll
   for (int m = 0; m < G::PREF; m++) {
-    const int q = min((int)threadIdx.x + m * BS, qmax);  // 4-column group in the fetched rows
+    const int q = min(tx + m * BS, qmax);  // 4-column group in the fetched rows
     v[m] = *(const uint2*)(base + 2 * (size_t)q);
   }
 }
@@ -121,9 +161,10 @@ __device__ __forceinline__ void dir_store(const Tables& t, DirLDS<BS, NPOW>& L, 
   if (p0 == INF32 || nr <= 0) return;
   nr = min(nr, DIR_CH);
   const int have = max(0, min(nr, lenc - p0));
+  const int tx = dir_tid();
 #pragma unroll
   for (int m = 0; m < G::PREF; m++) {
-    const int q = threadIdx.x + m * BS;
+    const int q = tx + m * BS;
     const int row = (4 * q) / N;
     if (row >= nr) continue;
     // LA16 + 1 per half = the LA + 2 encoding (LA <= 65,533: no carry); a row past the
@@ -198,9 +239,10 @@ __device__ __forceinline__ void dir_members_mb(const uint32_t* mb, uint32_t (&mw
   // 8-byte sc1 stores); 8-byte loads run at 0.54-0.70x the 16-byte rate
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc((void*)mb, 0, BS * G::CW * 4, 0x00020000);
+  const int tx = dir_tid();
 #pragma unroll
   for (int k = 0; k < G::CW / MVW; k++) {
-    const int off = (k * BS + (int)threadIdx.x) * MVW * 4;
+    const int off = (k * BS + tx) * MVW * 4;
     if constexpr (MVW == 4) {
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
       const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16);
@@ -227,7 +269,10 @@ template <int BS, int NPOW>
 __device__ __forceinline__ void dir_stage_member(const Tables& t, uint32_t* mb, int c, int p) {
   using G = DirGeo<BS, NPOW>;
   constexpr int MVW = G::MVW;
-  const int lane = threadIdx.x;  // < 64
+  int lane = threadIdx.x;  // < 64
+  // (opaque to the optimiser: the row addresses below are then formed here, once per
+  // round in one wave, and not kept in registers across the whole round loop)
+  asm volatile("" : "+v"(lane));
   const int N = t.N;
   if (4 * lane < NPOW) {
     unsigned long long x;
@@ -302,6 +347,139 @@ __device__ __forceinline__ int dir_count(const DirLDS<BS, NPOW>& L, int p, int p
   return cnt;
 }
 
+// ---- the narrow form (hge_narrow.h): the same counts over 8-bit fields relative to the
+// column's frontier position, four columns per word and compare ----
+
+// where column d's uint16 base sits in L.sB16 (halves; the row layout of the ring)
+template <int BS, int NPOW>
+__device__ __forceinline__ int dir_base_slot(int d) {
+  using G = DirGeo<BS, NPOW>;
+  const int w = d >> 1, part = w / G::CW;
+  return 2 * (part * G::PS + (w - part * G::CW)) + (d & 1);
+}
+
+// rows [lo, lo + H) of the 16-bit ring re-encoded into L.sN (row k = position lo + k;
+// "no row" entries and columns past N become 0, which passes no member value).
+// Returns the accumulator for nar_window_flag.
+template <int BS, int NPOW>
+__device__ __forceinline__ uint32_t dir_encode_window(const Tables& t, DirLDS<BS, NPOW>& L, int lo) {
+  using G = DirGeo<BS, NPOW>;
+  constexpr int GPR = NPOW / 4;  // 4-column groups per row
+  uint32_t mx = 0;
+  const int tx = dir_tid();
+#pragma unroll
+  for (int m = 0; m < G::NENC; m++) {
+    const int q = tx + m * BS;
+    if (q >= G::H * GPR) continue;
+    const int k = q / GPR, col = 4 * (q - k * GPR);
+    const int part = col / G::CPT, cp = col - part * G::CPT;
+    const int off = part * G::PS + cp / 2;
+    uint32_t word = hge_narrow::kNarGuard;
+    if (col < t.N) {
+      const uint2 la = *(const uint2*)(L.sLA + ((lo + k) & (G::W - 1)) * G::RS + off);
+      const uint2 cb = *(const uint2*)(L.sB16 + off);
+      word = hge_narrow::nar_enc_window4(la.x, la.y, cb.x, cb.y, mx);
+    }
+    L.sN[k * G::NRS + part * G::NPS + cp / 4] = word;
+  }
+  return mx;
+}
+
+// the thread's 16-bit member slice re-encoded against the bases of its columns;
+// returns the accumulator for nar_member_flag
+template <int BS, int NPOW>
+__device__ __forceinline__ uint32_t dir_encode_members(const DirLDS<BS, NPOW>& L, int part,
+                                                       const uint32_t (&mw)[DirGeo<BS, NPOW>::CW],
+                                                       uint32_t (&nw)[DirGeo<BS, NPOW>::NCW]) {
+  using G = DirGeo<BS, NPOW>;
+  const uint32_t* src = L.sB16 + part * G::PS;
+  uint32_t mn = 0xFFFFFFFFu;
+#pragma unroll
+  for (int k0 = 0; k0 < G::CW; k0 += G::VW) {
+    uint32_t cb[G::VW];
+    if constexpr (G::VW == 4) {
+      const uint4 q = *(const uint4*)(src + k0);
+      cb[0] = q.x;
+      cb[1] = q.y;
+      cb[2] = q.z;
+      cb[3] = q.w;
+    } else {
+      const uint2 q = *(const uint2*)(src + k0);
+      cb[0] = q.x;
+      cb[1] = q.y;
+    }
+#pragma unroll
+    for (int k = 0; k < G::VW; k += 2)
+      nw[(k0 + k) / 2] = hge_narrow::nar_enc_member4(mw[k0 + k], mw[k0 + k + 1], cb[k], cb[k + 1], mn);
+  }
+  return mn;
+}
+
+// dir_count over the narrow rows: window offset k (position lo + k, k < H) against the
+// narrow member slice.  One subtract, one mask and one population count per 4 columns.
+template <int BS, int NPOW>
+__device__ __forceinline__ int dir_count_n(const DirLDS<BS, NPOW>& L, int k, int part,
+                                           const uint32_t (&nw)[DirGeo<BS, NPOW>::NCW]) {
+  using G = DirGeo<BS, NPOW>;
+  const uint32_t* src = L.sN + k * G::NRS + part * G::NPS;
+  // v_bcnt_u32_b32 adds its count to an operand (left to the compiler, the sums are
+  // reassociated into a count, a count and a three-way add per two words); two
+  // accumulators, as in dir_count
+  uint32_t acc0 = 0, acc1 = 0;
+#pragma unroll
+  for (int k0 = 0; k0 < G::NCW; k0 += G::NVW) {
+    uint32_t a[G::NVW];
+    if constexpr (G::NVW == 4) {
+      const uint4 q = *(const uint4*)(src + k0);
+      a[0] = q.x;
+      a[1] = q.y;
+      a[2] = q.z;
+      a[3] = q.w;
+    } else if constexpr (G::NVW == 2) {
+      const uint2 q = *(const uint2*)(src + k0);
+      a[0] = q.x;
+      a[1] = q.y;
+    } else {
+      a[0] = src[k0];
+    }
+#pragma unroll
+    for (int j = 0; j < G::NVW; j++) {
+      const uint32_t ge = hge_narrow::nar_ge4(a[j], nw[k0 + j]);
+      if (j & 1) asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc1) : "v"(ge));
+      else asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc0) : "v"(ge));
+    }
+  }
+  int cnt = (int)(acc0 + acc1);
+  if constexpr (G::TPM > 1) cnt += __builtin_amdgcn_mov_dpp(cnt, 0xB1, 0xF, 0xF, false);
+  if constexpr (G::TPM > 2) cnt += __builtin_amdgcn_mov_dpp(cnt, 0x4E, 0xF, 0xF, false);
+  if constexpr (G::TPM > 4) cnt += __builtin_amdgcn_mov_dpp(cnt, 0x141, 0xF, 0xF, false);
+  if constexpr (G::TPM > 8) cnt += __builtin_amdgcn_mov_dpp(cnt, 0x140, 0xF, 0xF, false);
+  return cnt;
+}
+
+// The 16-bit member slice of round r again, for the paths that need it after the
+// narrow encode consumed it (the exact select, dir_probe_search): from MB[r & 1],
+// which no producer writes before this workgroup has published round r + 1, or in
+// the walk's first round from the FD table.  Call it before the round's publish.
+template <int BS, int NPOW>
+__device__ __forceinline__ void dir_members_reload(const Tables& t, const DirLDS<BS, NPOW>& L, const uint32_t* mb,
+                                                   bool first, int d, int part,
+                                                   uint32_t (&mw)[DirGeo<BS, NPOW>::CW]) {
+  using G = DirGeo<BS, NPOW>;
+  if (first) {
+    // (opaque to the optimiser, as in dir_stage_member: the table addresses of a rare
+    // path are formed here and not kept in registers across the round loop)
+    asm volatile("" : "+v"(d), "+v"(part));
+    dir_members_fd<BS, NPOW>(t, d, part, d < t.N ? L.sP[d] : INF32, mw);
+  } else {
+    dir_members_mb<BS, NPOW>(mb, mw);
+  }
+  if (d >= t.N) {
+#pragma unroll
+    for (int k = 0; k < G::CW; k++) mw[k] = 0xFFFFFFFFu;
+  }
+}
+
 // one probe: number of members strongly seen by candidate position p; `pass` =
 // this thread's member is strongly seen
 template <int BS, int NPOW>
@@ -326,6 +504,23 @@ __device__ __forceinline__ int dir_probe(const Tables& t, DirLDS<BS, NPOW>& L, i
   if (st) {
     L.sdbg[0] += t1 - t0;
     L.sdbg[1] += stamp() - t1;
+  }
+  return r;
+}
+
+// dir_probe over the narrow rows: window offset k < H against the narrow member slice
+template <int BS, int NPOW>
+__device__ __forceinline__ int dir_probe_n(const Tables& t, DirLDS<BS, NPOW>& L, int k, int part, int slot,
+                                           const uint32_t (&nw)[DirGeo<BS, NPOW>::NCW], bool& pass) {
+  pass = dir_count_n<BS, NPOW>(L, k, part, nw) >= t.SM;
+  const uint64_t b = __ballot(part == 0 && pass);
+  if ((threadIdx.x & 63) == 0) L.sCntW[slot][threadIdx.x >> 6] = (int)__builtin_popcountll(b);
+  __syncthreads();
+  int r = 0;
+#pragma unroll
+  for (int w = 0; w < BS / 64; w += 4) {
+    const int4 q = *(const int4*)&L.sCntW[slot][w];
+    r += q.x + q.y + q.z + q.w;
   }
   return r;
 }
@@ -388,10 +583,14 @@ __device__ int dir_probe_search(const Tables& t, int c, int lenc, DirLDS<BS, NPO
 // six per round, ~2.5k cycles each at N = 256); the counts here are the same
 // N^2 compares per step, with one barrier per round.
 // pb = this thread's member is strongly seen by the returned row.
-template <int BS, int NPOW>
+//
+// NAR: mw is the narrow slice and the counts are dir_count_n over L.sN (the caller
+// has established that the narrow form is exact this round); the fallback reloads
+// the 16-bit slice (dir_members_reload: mb, first).
+template <int BS, int NPOW, bool NAR>
 __device__ int dir_select(const Tables& t, int c, int lenc, DirLDS<BS, NPOW>& L, int d, int part,
-                          const uint32_t (&mw)[DirGeo<BS, NPOW>::CW], int& slot,
-                          uint2 (&pv)[DirGeo<BS, NPOW>::PREF], int& lo, bool& pb) {
+                          const uint32_t (&mw)[NAR ? DirGeo<BS, NPOW>::NCW : DirGeo<BS, NPOW>::CW], int& slot,
+                          uint2 (&pv)[DirGeo<BS, NPOW>::PREF], int& lo, bool& pb, const uint32_t* mb, bool first) {
   constexpr int H = DirGeo<BS, NPOW>::W / 2;
   constexpr int STEPS = H == 32 ? 5 : H == 16 ? 4 : 3;
   static_assert((1 << STEPS) == H, "window half is a power of two");
@@ -406,7 +605,10 @@ __device__ int dir_select(const Tables& t, int c, int lenc, DirLDS<BS, NPOW>& L,
 #pragma unroll
   for (int s = 0; s < STEPS; s++) {
     const int mid = (a + b) >> 1;
-    if (dir_count<BS, NPOW>(L, lo + mid, part, mw) >= SM) b = mid;
+    int cnt;
+    if constexpr (NAR) cnt = dir_count_n<BS, NPOW>(L, mid, part, mw);
+    else cnt = dir_count<BS, NPOW>(L, lo + mid, part, mw);
+    if (cnt >= SM) b = mid;
     else a = mid + 1;
   }
   // a == b == T_d, exact below e (e stands for "e or later"); members past N do not count
@@ -423,7 +625,8 @@ __device__ int dir_select(const Tables& t, int c, int lenc, DirLDS<BS, NPOW>& L,
   }
   // every wave: inclusive prefix over the H bins (DPP, HGE_DPP_SCAN: no LDS
   // permutes on the round's critical path), the first bin reaching SM
-  const int lane = threadIdx.x & 63;
+  int lane = threadIdx.x & 63;
+  asm volatile("" : "+v"(lane));  // (as in dir_stage_member: the bin's address is formed here)
   int v = lane < H ? L.sHist[lane] : 0;
   HGE_DPP_SCAN(v, dpp_add, 0);
   const uint64_t ge = __ballot(lane < H && v >= SM);
@@ -432,7 +635,25 @@ __device__ int dir_select(const Tables& t, int c, int lenc, DirLDS<BS, NPOW>& L,
     pb = a <= ks;
     return lo + ks;
   }
-  return dir_probe_search<BS, NPOW>(t, c, lenc, L, part, mw, slot, pv, lo, pb, e);
+  if constexpr (NAR) {
+    // The chain ends inside the half window (every call's last rounds: most chains have
+    // no next frontier row yet): offset e is its last row and is in the narrow rows, so
+    // one narrow probe settles it as dir_probe_search would (that row, or none), without
+    // loading the 16-bit slice again.
+    if (lenc - lo <= H) {
+      bool ps;
+      if (dir_probe_n<BS, NPOW>(t, L, e, part, slot++, mw, ps) >= SM) {
+        pb = ps;
+        return lo + e;
+      }
+      return INF32;
+    }
+    uint32_t mx[DirGeo<BS, NPOW>::CW];
+    dir_members_reload<BS, NPOW>(t, L, mb, first, d, part, mx);
+    return dir_probe_search<BS, NPOW>(t, c, lenc, L, part, mx, slot, pv, lo, pb, e);
+  } else {
+    return dir_probe_search<BS, NPOW>(t, c, lenc, L, part, mw, slot, pv, lo, pb, e);
+  }
 }
 
 template <int BS, int NPOW>
@@ -441,7 +662,9 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
                                                       int Rprev, uint64_t* gran,
                                                       int32_t* err, uint64_t* ssc, uint32_t* mbuf,
                                                       uint64_t* dbg, const int32_t* start, int32_t* hist,
-                                                      int hmax, const int32_t* stopcut, int extra, int stall_ep) {
+                                                      int hmax, const int32_t* stopcut, int extra, int stall_ep,
+                                                      int force_exact, unsigned long long* paths,
+                                                      unsigned long long* paths_next) {
   // History mode (hist != nullptr; a walker of the cross-GPU split, babble_amd/dist.py):
   // the walk starts at the frontier `start` (rlo = 0, Rprev = 0), writes frontier
   // row j to hist[j * N + c] instead of C, the ssc bits of row j to ssc row j, and
@@ -451,11 +674,18 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
   // stall_ep > 0 (tests, HGE_TEST_HANDOFF_STALL): at hand-off epoch stall_ep chain 0
   // does not publish and every workgroup gives up at once, as on a timed-out poll, so
   // the other chains' rows of that round are written and chain 0's is not.
+  // force_exact (tests, HGE_TEST_DIR_EXACT): every round takes the 16-bit select.
+  // paths[0], paths[1] += this chain's rounds selected over the narrow rows / by the
+  // 16-bit select (one add per workgroup, at exit); chain 0 clears paths_next[0..1], the
+  // counters of the next walk on the stream.
   using G = DirGeo<BS, NPOW>;
   // rlo_dev: the first round to recompute, read here (INF32: nothing to do)
   if (rlo_dev) {
     rlo = *rlo_dev;
-    if (rlo == INF32) return;
+    if (rlo == INF32) {
+      if (blockIdx.x == 0 && threadIdx.x == 0 && paths) paths_next[0] = paths_next[1] = 0;
+      return;
+    }
   }
   // HGE_STAMPS diagnostics (workgroup 0, thread 0): cycles per section into dbg[0..8]
   // (6 = probes; 7, 8 = member-load issue and arrival inside section 0)
@@ -488,11 +718,19 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
     }
     L.sP[tid] = P;
   }
+  if constexpr (G::NARROW) {  // every column's base (columns past N: 0, their member values are unset)
+    if (tid < NPOW) ((uint16_t*)L.sB16)[dir_base_slot<BS, NPOW>(tid)] = tid < N ? (uint16_t)hge_narrow::nar_base16(L.sP[tid]) : 0;
+  }
   if (tid == 0) {
     L.s_stamp = stamping ? 1 : 0;
     L.sdbg[0] = L.sdbg[1] = 0;
+    L.sEx[0] = L.sEx[1] = 0;
   }
   __syncthreads();
+  if constexpr (G::NARROW) {
+    if (tid < N && hge_narrow::nar_base_too_large(L.sP[tid])) atomicOr(&L.sEx[rlo & 1], 1);
+  }
+  int n_nar = 0, n_ex = 0;  // this chain's rounds by select path
   const int rcap = hist ? hmax : t.Rcap;
   int extra_left = -1;  // history mode: rows still to walk after passing stopcut
   uint2 pv[G::PREF];
@@ -503,6 +741,7 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
   // by each wave right after its own poll of the previous round (below)
   uint32_t mw[G::CW];
   dir_members_fd<BS, NPOW>(t, d, part, d < N ? L.sP[d] : INF32, mw);
+  if constexpr (G::NARROW) __syncthreads();  // the first window is stored: the round's top re-encodes it
   for (int r = rlo;; r++) {
     if (r + 1 >= rcap) {
       if (c == 0 && tid == 0) {
@@ -519,50 +758,84 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
     if (tid < DIR_MAXP) L.sCnt[tid] = 0;
     if (tid < 8) L.sBits[tid] = 0;
     if (tid < DirGeo<BS, NPOW>::W / 2) L.sHist[tid] = 0;
-    if (tid == 0) L.sFlag[(r + 1) & 1] = 0;  // read after the previous round's poll barrier
-    __syncthreads();  // window stored, counters clear
-    DSTAMP(0);
+    if (tid == 0) {
+      L.sFlag[(r + 1) & 1] = 0;  // read after the previous round's poll barrier
+      L.sEx[(r + 1) & 1] = 0;    // (set from that barrier on, read after the next round's first one)
+    }
     const int Pc = L.sP[c];
     const int cur = (r + 1 < Rprev) ? t.C[(size_t)(r + 1) * N + c] : INF32;
-    int slot = 0;
-    int nxt = INF32;
-    bool pb = false, have_bits = false;
-    if (Pc != INF32) {
-      if (cur != INF32) {
-        nxt = cur;
-      } else {
-        const int s = dir_select<BS, NPOW>(t, c, lenc, L, d, part, mw, slot, pv, lo, pb);
-        nxt = s < lenc ? s : INF32;
-        have_bits = nxt != INF32;
+    // A round that selects re-encodes its window's first half and the member slice
+    // relative to the frontier (complete since the poll barrier: L.sP, L.sB16, and the
+    // window rows were stored before it), so the barrier below also publishes L.sN.
+    // mw is spent by this: what needs the 16-bit slice afterwards reloads it.
+    uint32_t nw[G::NCW];
+    bool enc = false;
+    if constexpr (G::NARROW) {
+      enc = Pc != INF32 && cur == INF32 && lo != INF32 && lo < lenc && !force_exact;
+      if (enc) {  // block-uniform
+        const uint32_t mx = dir_encode_window<BS, NPOW>(t, L, lo);
+        const uint32_t mn = dir_encode_members<BS, NPOW>(L, part, mw, nw);
+        if (hge_narrow::nar_window_flag(mx) || hge_narrow::nar_member_flag(mn)) L.sEx[r & 1] = 1;
       }
     }
-    DSTAMP(1);
-    if (stamping) st_acc[6] += slot;
+    __syncthreads();  // window stored, counters clear
+    DSTAMP(0);
+    int slot = 0;
+    int nxt = INF32;
+    bool pb = false;
+    const bool stall = stall_ep > 0 && r - rlo + 1 == stall_ep;
     // publish C_{r+1}[c]: wave 0 stages the next member row, drains its stores,
     // then lane 0 stores the granule
-    const bool stall = stall_ep > 0 && r - rlo + 1 == stall_ep;
-    if (tid < 64 && !(stall && c == 0)) {
-      dir_stage_member<BS, NPOW>(t, mbp[(r + 1) & 1], c, nxt);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (tid == 0) {
-        if (hist) hist[(size_t)(r + 1) * N + c] = nxt;
-        else if (nxt != INF32 && cur == INF32) t.C[(size_t)(r + 1) * N + c] = nxt;
-        const uint64_t g = ((uint64_t)(uint32_t)(r - rlo + 1) << 32) | (uint32_t)nxt;
-        __hip_atomic_store(gr[(r + 1) & 1] + c, (unsigned long long)g, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+    auto publish = [&]() {
+      DSTAMP(1);
+      if (stamping) st_acc[6] += slot;
+      if (tid < 64 && !(stall && c == 0)) {
+        dir_stage_member<BS, NPOW>(t, mbp[(r + 1) & 1], c, nxt);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (tid == 0) {
+          if (hist) hist[(size_t)(r + 1) * N + c] = nxt;
+          else if (nxt != INF32 && cur == INF32) t.C[(size_t)(r + 1) * N + c] = nxt;
+          const uint64_t g = ((uint64_t)(uint32_t)(r - rlo + 1) << 32) | (uint32_t)nxt;
+          __hip_atomic_store(gr[(r + 1) & 1] + c, (unsigned long long)g, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+        }
       }
+    };
+    if (Pc == INF32) {
+      publish();
+    } else if (cur != INF32) {
+      // a frontier row kept from an earlier batch: no select (mw is still the 16-bit
+      // slice), one probe for its strongly-see bits
+      nxt = cur;
+      publish();
+      if (nxt < lo || nxt >= lo + DirGeo<BS, NPOW>::W) {
+        __syncthreads();
+        lo = nxt;
+        dir_load<BS, NPOW>(t, L, c, lo, DirGeo<BS, NPOW>::W, lenc, pv);
+        __syncthreads();
+      }
+      pb = dir_count<BS, NPOW>(L, nxt, part, mw) >= t.SM;
+    } else {
+      int s;
+      if constexpr (G::NARROW) {
+        const uint32_t* mbr = mbp[r & 1];
+        if (enc && L.sEx[r & 1] == 0) {
+          n_nar++;
+          s = dir_select<BS, NPOW, true>(t, c, lenc, L, d, part, nw, slot, pv, lo, pb, mbr, r == rlo);
+        } else {  // a round whose narrow form is not exact, or the test hook
+          n_ex++;
+          dir_members_reload<BS, NPOW>(t, L, mbr, r == rlo, d, part, mw);
+          s = dir_select<BS, NPOW, false>(t, c, lenc, L, d, part, mw, slot, pv, lo, pb, mbr, r == rlo);
+        }
+      } else {
+        n_ex++;
+        s = dir_select<BS, NPOW, false>(t, c, lenc, L, d, part, mw, slot, pv, lo, pb, nullptr, false);
+      }
+      nxt = s < lenc ? s : INF32;
+      publish();
     }
     // strongly-see bits of C_{r+1}[c] against the members of round r
     if (nxt != INF32) {
-      if (!have_bits) {  // a frontier row kept from an earlier batch: one more probe
-        if (nxt < lo || nxt >= lo + DirGeo<BS, NPOW>::W) {
-          __syncthreads();
-          lo = nxt;
-          dir_load<BS, NPOW>(t, L, c, lo, DirGeo<BS, NPOW>::W, lenc, pv);
-          __syncthreads();
-        }
-        pb = dir_count<BS, NPOW>(L, nxt, part, mw) >= t.SM;
-      }
       if (part == 0 && d < N && pb) atomicOr(&L.sBits[d >> 5], 1u << (d & 31));
       __syncthreads();  // also: every wave is done with this round's window
       if (tid < NW)
@@ -598,6 +871,8 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
     // load only after the slowest chain had published).  Each wave loads only
     // bytes whose flags it polled itself (MI355X_MICROARCH.md, Valid forms, row 1).
     {
+      const int tp = dir_tid();
+      const int d = tp / G::TPM, part = tp - d * G::TPM;  // (formed here, see dir_tid)
       const unsigned ep = (unsigned)(r - rlo + 1);
       const gu64_t* g = gr[(r + 1) & 1];
       unsigned spins = 0;
@@ -618,7 +893,14 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
         __builtin_amdgcn_s_sleep(1);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (part == 0 && d < N) L.sP[d] = P;
+      if (part == 0 && d < N) {
+        L.sP[d] = P;
+        if constexpr (G::NARROW) ((uint16_t*)L.sB16)[dir_base_slot<BS, NPOW>(d)] = (uint16_t)hge_narrow::nar_base16(P);
+      }
+      if constexpr (G::NARROW) {  // a base the narrow form cannot take: the next round selects in 16 bits
+        if (__ballot(part == 0 && d < N && hge_narrow::nar_base_too_large(P)) != 0 && (threadIdx.x & 63) == 0)
+          L.sEx[(r + 1) & 1] = 1;
+      }
       const bool any = __ballot(d < N && P != INF32) != 0;
       const bool notpast = stopcut && __ballot(part == 0 && d < N && P < stopcut[d]) != 0;  // INF32 passes
       if ((threadIdx.x & 63) == 0 && (any || notpast || fail))
@@ -627,7 +909,12 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
         atomicOr(err, 1);
         atomicOr(rstate + 1, 4);  // the downstream kernels stand down, as on overflow
       }
-      if (!fail) dir_members_mb<BS, NPOW>(mbp[(r + 1) & 1], mw);
+      if (!fail) {
+        dir_members_mb<BS, NPOW>(mbp[(r + 1) & 1], mw);
+      } else {  // (the walk ends below: no round reads the slice again, so it need not stay in registers)
+#pragma unroll
+        for (int k = 0; k < G::CW; k++) mw[k] = 0;
+      }
     }
     __syncthreads();  // every wave has polled (and stored its window rows)
     DSTAMP(4);
@@ -648,6 +935,11 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
       }
     }
   }
+  if (tid == 0 && paths) {
+    atomicAdd(paths, (unsigned long long)n_nar);
+    atomicAdd(paths + 1, (unsigned long long)n_ex);
+    if (c == 0) paths_next[0] = paths_next[1] = 0;
+  }
   if (stamping) {
     for (int q = 0; q < 9; q++) dbg[q] += st_acc[q];
     dbg[9] += L.sdbg[0];
@@ -658,10 +950,10 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
 }
 
 template __global__ void k_rounds_direct<1024, 64>(Tables, const int32_t*, const int32_t*, int32_t*, int, const int32_t*, int,
-    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int);
+    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, unsigned long long*, unsigned long long*);
 template __global__ void k_rounds_direct<1024, 128>(Tables, const int32_t*, const int32_t*, int32_t*, int, const int32_t*, int,
-    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int);
+    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, unsigned long long*, unsigned long long*);
 template __global__ void k_rounds_direct<1024, 256>(Tables, const int32_t*, const int32_t*, int32_t*, int, const int32_t*, int,
-    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int);
+    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, unsigned long long*, unsigned long long*);
 
 }  // namespace hge

@@ -73,7 +73,7 @@ EXPORTS = [
     "hge_fame", "hge_round_events", "hge_round_received", "hge_consensus_timestamp",
     "hge_consensus_timestamp_sources",
     "hge_ancestor", "hge_self_ancestor", "hge_see", "hge_strongly_see",
-    "hge_oldest_self_ancestor_to_see", "hge_coordinates", "hge_coordinate_sweeps", "hge_host_syncs", "hge_frontier_fallbacks",
+    "hge_oldest_self_ancestor_to_see", "hge_coordinates", "hge_coordinate_sweeps", "hge_walk_select_paths", "hge_host_syncs", "hge_frontier_fallbacks",
     "hge_stage_times",
     "hge_set_profiling", "hge_reset_kernel_stats", "hge_kernel_stats",
     "hge_consensus_log", "hge_event_rounds", "hge_event_received", "hge_set_cache_size",
@@ -166,6 +166,8 @@ def lib():
     L.hge_stage_times.argtypes = [vp, P(ctypes.c_float), ctypes.c_int]
     L.hge_coordinate_sweeps.restype = ctypes.c_int32
     L.hge_coordinate_sweeps.argtypes = [vp]
+    if hasattr(L, "hge_walk_select_paths"):  # (a diagnostic build of an older tree, HGE_LIB, lacks it)
+        L.hge_walk_select_paths.argtypes = [vp, P(i64), P(i64)]
     if hasattr(L, "hge_gob_encode_wire_events"):
         L.hge_gob_encode_wire_events.argtypes = [vp, i64, P(ctypes.c_uint8), P(i64), i32, P(ctypes.c_uint8), i64,
                                                  P(i64)]
@@ -672,6 +674,13 @@ class Engine:
     def coordinate_sweeps(self):
         """lastAncestors sweeps of the last coordinate pass (hge_coords.hip)."""
         return self.L.hge_coordinate_sweeps(self.h)
+
+    def walk_select_paths(self):
+        """(narrow, exact): chain-rounds of the last direct rounds walk selected over the
+        8-bit frontier-relative rows, and by the 16-bit select (hge_rounds_direct.hip)."""
+        nar, ex = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self.L.hge_walk_select_paths(self.h, ctypes.byref(nar), ctypes.byref(ex)))
+        return nar.value, ex.value
 
     def host_syncs(self):
         """Host round trips so far (waits on the engine stream)."""

@@ -455,6 +455,11 @@ int hge_stage_times(hge_engine* h, float* ms_out, int cap);
  * 32 < N <= 256 (hge_coords_win.hip), Jacobi sweeps otherwise (hge_coords.hip);
  * the last one confirms the fixed point (a single window needs one pass). */
 int32_t hge_coordinate_sweeps(hge_engine* h);
+/* Chain-rounds of the last direct rounds walk (DivideRounds for 32 < N, N % 4 == 0,
+ * or hge_frontier_walk) by select path: over the 8-bit frontier-relative rows, and
+ * by the 16-bit select (a round whose values leave the narrow range, or
+ * HGE_TEST_DIR_EXACT=1).  Both 0 when no such walk has run. */
+int hge_walk_select_paths(hge_engine* h, int64_t* narrow, int64_t* exact);
 /* Host round trips so far: the number of times the host has waited on the
  * engine's stream (each readback of a control value or result is one). */
 int64_t hge_host_syncs(hge_engine* h);
