@@ -3584,6 +3584,7 @@ int hge_replay(hge_engine* h, const hge_event* ev, int64_t n_sub, const int64_t*
 
 int64_t hge_event_count(hge_engine* h) { return h->n_events; }
 int32_t hge_participants(hge_engine* h) { return h->N; }
+int32_t hge_device(hge_engine* h) { return h->device; }
 int32_t hge_rounds(hge_engine* h) { return std::max(h->R_div, h->R_set); }
 int32_t hge_last_consensus_round(hge_engine* h) { return h->lcr; }
 int32_t hge_last_committed_round_events(hge_engine* h) { return h->lcre; }

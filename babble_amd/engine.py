@@ -82,6 +82,9 @@ EXPORTS = [
     "hge_round_diff", "hge_set_round", "hge_round_event_ids", "hge_split_begin", "hge_frontier_guess",
     "hge_frontier_walk", "hge_split_finish", "hge_frontier_rows", "hge_split_plan", "hge_split_exchange", "hge_split_run", "hge_split_emulate",
     "hge_verify_events", "hge_sha256_batch", "hge_ingest", "hge_fame_table",
+    # Event.Verify on the device (opt-in, hge_verify.hip)
+    "hge_sha256_batch_device", "hge_ecdsa_p256_verify_digests_device", "hge_verify_events_device",
+    "hge_ingest_device", "hge_device",
     # the standalone Store (host only; the Go shim's NewInmemStore, tests/abi/hge_store_test.cpp)
     "hge_store_create", "hge_store_destroy", "hge_store_set_event", "hge_store_has_event",
     "hge_store_participant_events", "hge_store_participant_event", "hge_store_last_from",
@@ -222,6 +225,14 @@ def lib():
     L.hge_sha256_batch.argtypes = [i64, u8p, P(i64), i32, u8p]
     L.hge_ingest.argtypes = [vp, ctypes.c_void_p, i64, u8p, P(i64), u8p, u8p, i64, i32, P(i32), P(i64),
                              P(ctypes.c_double)]
+    L.hge_sha256_batch_device.argtypes = [i64, u8p, P(i64), i32, u8p]
+    L.hge_ecdsa_p256_verify_digests_device.argtypes = [i64, u8p, u8p, i32, P(i32), u8p, i32, P(i32)]
+    L.hge_verify_events_device.argtypes = [i64, u8p, P(i64), u8p, i32, P(i32), u8p, i32, u8p, P(i32),
+                                           P(ctypes.c_double)]
+    L.hge_ingest_device.argtypes = [vp, ctypes.c_void_p, i64, u8p, P(i64), u8p, u8p, i64, i64, P(i32), P(i64),
+                                    P(ctypes.c_double)]
+    L.hge_device.argtypes = [vp]
+    L.hge_device.restype = i32
     L.hge_set_profiling.argtypes = [vp, ctypes.c_int]
     L.hge_reset_kernel_stats.argtypes = [vp]
     L.hge_kernel_stats.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
@@ -283,6 +294,60 @@ def verify_events(bodies, pubs, sigs, threads=0):
     if rc != 0:
         raise HgeError(rc, "hge_verify_events failed")
     return ok[:n].astype(bool), hashes[:n]
+
+
+def sha256_batch_device(data, device=0):
+    """SHA-256 of each byte string on the device (hge_sha256_batch_device): uint8[n, 32]."""
+    flat, off = _flat(data)
+    n = len(off) - 1
+    out = np.zeros((max(n, 1), 32), np.uint8)
+    rc = lib().hge_sha256_batch_device(n, _pu8(flat), _p64(off), device, _pu8(out))
+    if rc != 0:
+        raise HgeError(rc, "hge_sha256_batch_device failed")
+    return out[:n]
+
+
+def _keys_idx(keys, key_idx, n):
+    keys = np.ascontiguousarray(keys, np.uint8).reshape(-1, 65)
+    key_idx = np.ascontiguousarray(key_idx, np.int32).reshape(n)
+    if len(keys) == 0:
+        keys = np.zeros((1, 65), np.uint8)  # (a pointer for ctypes; n_keys stays 0)
+        return keys, 0, key_idx
+    return keys, len(keys), key_idx
+
+
+def verify_digests_device(digests, keys, key_idx, sigs, device=0):
+    """ecdsa.Verify for a batch on the device (hge_ecdsa_p256_verify_digests_device):
+    ok bool[n].  digests uint8[n, 32]; keys uint8[n_keys, 65]; key_idx int32[n], event
+    i's key is keys[key_idx[i]]; sigs uint8[n, 64] (r || s)."""
+    digests = np.ascontiguousarray(digests, np.uint8).reshape(-1, 32)
+    n = len(digests)
+    keys, n_keys, key_idx = _keys_idx(keys, key_idx, n)
+    sigs = np.ascontiguousarray(sigs, np.uint8).reshape(n, 64)
+    ok = np.zeros(max(n, 1), np.int32)
+    rc = lib().hge_ecdsa_p256_verify_digests_device(n, _pu8(digests), _pu8(keys), n_keys, _p32(key_idx), _pu8(sigs),
+                                                    device, _p32(ok))
+    if rc != 0:
+        raise HgeError(rc, "hge_ecdsa_p256_verify_digests_device failed")
+    return ok[:n].astype(bool)
+
+
+def verify_events_device(bodies, keys, key_idx, sigs, device=0):
+    """Event.Verify for a batch on the device (hge_verify_events_device): returns
+    (ok bool[n], body hashes uint8[n, 32], device ms of the kernels).  bodies: list of
+    bytes or (flat, off); keys uint8[n_keys, 65]; key_idx int32[n]; sigs uint8[n, 64]."""
+    flat, off = _flat(bodies)
+    n = len(off) - 1
+    keys, n_keys, key_idx = _keys_idx(keys, key_idx, n)
+    sigs = np.ascontiguousarray(sigs, np.uint8).reshape(n, 64)
+    ok = np.zeros(max(n, 1), np.int32)
+    hashes = np.zeros((max(n, 1), 32), np.uint8)
+    ms = ctypes.c_double()
+    rc = lib().hge_verify_events_device(n, _pu8(flat), _p64(off), _pu8(keys), n_keys, _p32(key_idx), _pu8(sigs),
+                                        device, _pu8(hashes), _p32(ok), ctypes.byref(ms))
+    if rc != 0:
+        raise HgeError(rc, "hge_verify_events_device failed")
+    return ok[:n].astype(bool), hashes[:n], ms.value
 
 
 class GobTime(ctypes.Structure):
@@ -489,6 +554,26 @@ class Engine:
         tm = (ctypes.c_double * 3)()
         rc = self.L.hge_ingest(self.h, ev.ctypes.data, n, _pu8(flat), _p64(off), _pu8(keys), _pu8(sigs), int(k),
                                threads, _p32(status), ctypes.byref(acc), tm)
+        if rc in (-8, -9, -10):  # argument, device or internal error (admission errors end the stream)
+            raise HgeError(rc, self.L.hge_last_error(self.h).decode())
+        return rc, status[:n], acc.value, {"verify_ms": tm[0], "device_ms": tm[1], "wall_ms": tm[2]}
+
+    def ingest_device(self, ev, bodies, keys, sigs, k, verify_block=0):
+        """hge_ingest_device: ingest() with the signatures checked on this engine's device,
+        in blocks of verify_block events (0: 65,536) each verified to completion before its
+        first event is inserted.  Same arguments otherwise and the same return;
+        times["verify_ms"] is the time of the verify blocks (nothing hides it)."""
+        ev = np.ascontiguousarray(ev, EVENT_DTYPE)
+        flat, off = _flat(bodies)
+        n = len(ev)
+        assert len(off) == n + 1
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(self.n, 65)
+        sigs = np.ascontiguousarray(sigs, np.uint8).reshape(n, 64)
+        status = np.zeros(max(n, 1), np.int32)
+        acc = ctypes.c_int64()
+        tm = (ctypes.c_double * 3)()
+        rc = self.L.hge_ingest_device(self.h, ev.ctypes.data, n, _pu8(flat), _p64(off), _pu8(keys), _pu8(sigs),
+                                      int(k), int(verify_block), _p32(status), ctypes.byref(acc), tm)
         if rc in (-8, -9, -10):  # argument, device or internal error (admission errors end the stream)
             raise HgeError(rc, self.L.hge_last_error(self.h).decode())
         return rc, status[:n], acc.value, {"verify_ms": tm[0], "device_ms": tm[1], "wall_ms": tm[2]}

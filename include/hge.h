@@ -8,8 +8,9 @@
  *
  * Events are identified by dense engine ids assigned in insertion order (the
  * shim keeps the hash <-> id map).  The signature check and hashing of
- * InsertEvent's front half run on host cores (hge_verify_events, hge_ingest
- * below); the consensus entry points take verified hge_event records.
+ * InsertEvent's front half run on host cores by default (hge_verify_events,
+ * hge_ingest below) or, opt-in, on the device (hge_verify_events_device,
+ * hge_ingest_device); the consensus entry points take verified hge_event records.
  *
  * Threading: one handle is used by one thread at a time (the reference
  * serialises Core under Node.coreLock, node/node.go:167-169).
@@ -131,6 +132,47 @@ int hge_sha256_batch(int64_t n, const uint8_t* data, const int64_t* off, int32_t
 int hge_ingest(hge_engine* h, const hge_event* ev, int64_t n, const uint8_t* bodies, const int64_t* body_off,
                const uint8_t* keys, const uint8_t* sigs, int64_t k, int32_t threads, int32_t* status_out,
                int64_t* n_accepted, double* times_out);
+
+/* ---- device ingest pipeline (opt-in; hge_verify.hip) ------------ */
+/* The host pipeline above is the default and the reference: it needs no device time
+ * and overlaps the consensus kernels.  The entry points below run the same checks as
+ * HIP kernels, one thread per event, for streams whose signature work exceeds what the
+ * host cores deliver (a wide online stream, a bulk replay of a signed stream); DESIGN.md
+ * §4.9 has the measured rates of both.  All are synchronous, take a device ordinal,
+ * allocate their own buffers and stream, and work in chunks of at most 2^20 events.
+ * n == 0 returns HGE_OK and argument errors HGE_ERR_ARG before the device is touched.
+ *
+ * SHA-256 of n byte strings data[off[i] .. off[i+1]) into out[32 i] (EventBody.Hash,
+ * event.go:60-66; Event.Hash, event.go:169-179): hge_sha256_batch on the device. */
+int hge_sha256_batch_device(int64_t n, const uint8_t* data, const int64_t* off, int32_t device, uint8_t* out);
+/* ecdsa.Verify (crypto.Verify, crypto/utils.go:60-64) of n signatures sigs[64 i] = r || s
+ * over the 32-byte digests[32 i] under keys[65 key_idx[i]], n_keys uncompressed P-256
+ * points decoded as by elliptic.Unmarshal (crypto.ToECDSAPub, crypto/utils.go:40-46: a key
+ * that is not 0x04 || X || Y on the curve verifies nothing).  ok_out[i] = 0 / 1.  A
+ * key_idx outside [0, n_keys) is HGE_ERR_ARG. */
+int hge_ecdsa_p256_verify_digests_device(int64_t n, const uint8_t* digests, const uint8_t* keys, int32_t n_keys,
+                                         const int32_t* key_idx, const uint8_t* sigs, int32_t device,
+                                         int32_t* ok_out);
+/* Event.Verify (event.go:140-150) for n events: hge_verify_events with the keys given
+ * once, keys[65 c], and a key index per event (hge_ingest's shape: the participants are
+ * few and every event reuses one of their keys).  body_hash_out and device_ms may be
+ * NULL; *device_ms = time of the kernels between HIP events, copies excluded. */
+int hge_verify_events_device(int64_t n, const uint8_t* bodies, const int64_t* body_off, const uint8_t* keys,
+                             int32_t n_keys, const int32_t* key_idx, const uint8_t* sigs, int32_t device,
+                             uint8_t* body_hash_out, int32_t* ok_out, double* device_ms);
+/* hge_ingest with the signatures checked on the engine's own device (hashgraph.go:330-336
+ * before node/core.go:179-202's insert + RunConsensus): the same batches of k, the same
+ * end of the stream at the first bad signature (HGE_ERR_SIGNATURE, the events before it
+ * in its batch inserted and run through consensus), a creator id outside [0, N) left to
+ * admission, status_out / n_accepted as there.  Signatures are checked in blocks of
+ * verify_block events (rounded up to a multiple of k; <= 0: 65,536), each block to
+ * completion before its first event is inserted: the verify kernels never run beside the
+ * consensus kernels, whose wide rounds walk needs every CU it was sized for.
+ * times_out (may be NULL): [0] ms in the verify blocks (none of it hidden), [1] ms inside
+ * the insert + consensus calls, [2] wall ms. */
+int hge_ingest_device(hge_engine* h, const hge_event* ev, int64_t n, const uint8_t* bodies, const int64_t* body_off,
+                      const uint8_t* keys, const uint8_t* sigs, int64_t k, int64_t verify_block,
+                      int32_t* status_out, int64_t* n_accepted, double* times_out);
 
 /* ---- consensus (node/core.go:179-202) --------------------------------------- */
 int hge_divide_rounds(hge_engine* h);          /* hashgraph.go:573-588 */
@@ -269,6 +311,7 @@ int hge_split_finish(hge_engine* h, const int32_t* rows, const uint64_t* ssc, in
 /* ---- state queries --------------------------------------------------------- */
 int64_t hge_event_count(hge_engine* h);
 int32_t hge_participants(hge_engine* h);
+int32_t hge_device(hge_engine* h); /* the device ordinal given to hge_create */
 int32_t hge_rounds(hge_engine* h);                    /* Store.Rounds()            */
 int32_t hge_last_consensus_round(hge_engine* h);      /* -1 = nil                  */
 int32_t hge_last_committed_round_events(hge_engine* h);
