@@ -1615,8 +1615,12 @@ struct hge_engine {
       const char* hs = getenv("HGE_TEST_HANDOFF_STALL");
       int stall_ep = hs ? atoi(hs) : 0;
       int force_exact = walk_force_exact();
+      // tests: at this hand-off epoch chain 1 flags its staged member row (a fine one)
+      const char* mf = getenv("HGE_TEST_DIR_MEMBER_FLAG");
+      int mflag_ep = mf ? atoi(mf) : 0;
       void* dargs[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
-                       &nostart, &nohist, &hmax, &nostart, &extra, &stall_ep, &force_exact, &paths, &paths_next};
+                       &nostart, &nohist, &hmax, &nostart, &extra, &stall_ep, &force_exact, &mflag_ep, &paths,
+                       &paths_next};
       prof_begin("k_rounds_direct");
       HIPCHK(launch_resident(direct_fn(), dim3(N), dim3(1024), dargs));
       prof_end();
@@ -1632,9 +1636,10 @@ struct hge_engine {
       h2d(rstate + 1, &down, 4);
     }
   }
-  // the direct walk's staged member rows: two parity blocks of npow rows x npow/2 packed words
+  // the direct walk's staged member rows: two parity blocks of npow rows x npow/2 packed
+  // words, then two of npow x npow bytes, the same rows in 8-bit form (hge_narrow.h)
   uint32_t* walk_mb() {
-    s_mb.need((size_t)npow() * npow());
+    s_mb.need((size_t)npow() * npow() + (size_t)npow() * npow() / 2);
     return s_mb.p;
   }
   // The walk's select-path counters (hge_walk_select_paths): two slots of {narrow, exact},
@@ -3487,8 +3492,9 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
   const int32_t* st0 = h->s_hstate.p;
   int32_t* hist = h->s_hist.p;
   int hm = hmax, ex = std::max(0, (int)extra), nostall = 0, force_exact = hge_engine::walk_force_exact();
+  int nomflag = 0;
   void* args[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
-                  &st0, &hist, &hm, &cut, &ex, &nostall, &force_exact, &paths, &paths_next};
+                  &st0, &hist, &hm, &cut, &ex, &nostall, &force_exact, &nomflag, &paths, &paths_next};
   h->prof_begin("k_rounds_direct_walk");
   HIPCHK(h->launch_resident(h->direct_fn(), dim3(N), dim3(1024), args));
   h->prof_end();

@@ -5,22 +5,31 @@
 //
 // The kernel's 16-bit operands are LAe = LA + 2 (0 = no row) and FDe = FD + 1
 // (0xFFFF = unset / no member), two columns per word; a column passes when
-// LAe > FDe (LA >= FD).  Per column i the narrow form is relative to the frontier
-// position C = C_r[i] (kept as a uint16, nar_base16):
-//   window value  a = min(LAe -sat C, 126)      = clamp(LA - C + 2, 0, 126)
-//   member value  b = min(FDe -sat C, 126) + 1  = clamp(FD - C + 2, 1, 127)
+// LAe > FDe (LA >= FD).  Per column i the narrow form is relative to a base B[i]
+// that both sides share (kept as a uint16, nar_base16):
+//   window value  a = min(LAe -sat B, 126)      = clamp(LA - B + 2, 0, 126)
+//   member value  b = min(FDe -sat B, 126) + 1  = clamp(FD - B + 2, 1, 127)
 // four columns per word, each 7-bit value under a guard bit: the window words are
 // stored with the guard bits set, so aw - bw never borrows across fields and leaves
 // [a >= b] in each guard bit (nar_ge4).
 //
-// a >= b equals LAe > FDe unless
-//   (i)  some a saturates (LAe - C >= 126: the row runs past the range), or
-//   (ii) a finite FD lies below its base (FDe <= C: the clamp at 1 loses the order),
+// a >= b equals LAe > FDe, whatever the base, unless
+//   (i)  some a saturates (LAe - B >= 126: the row runs past the range), or
+//   (ii) a finite FD lies below its base (FDe <= B: the clamp at 1 loses the order),
 // which the encoders report (nar_window_flag, nar_member_flag); the kernel then
 // takes the 16-bit select for that round.  An unset FDe = 0xFFFF must encode as 127,
-// which holds while C <= kNarBaseMax; the kernel checks the bases for that.  A
+// which holds while B <= kNarBaseMax; the kernel checks the bases for that.  A
 // chain without a frontier position has the base kNarBaseNone: its window values
 // are at most 1, an unset member value is 2 and a finite one raises (ii).
+//
+// The base of round r is the PREVIOUS frontier, B_r[i] = C_{r-1}[i] (the walk's first
+// round: C_r itself): the workgroup that stages a member row for round r does so
+// before it knows the other chains' C_r, but it holds C_{r-1} in full, so it stages
+// the row already encoded (nar_mb_word says where) and no consumer encodes it again.
+// (ii) cannot get worse by that: a finite FD[m_d][i] of a round-r member is the
+// position of a descendant of a round-r event, hence >= C_r[i] >= C_{r-1}[i].  The
+// window values grow by one round's advance of the column (at most ~33 at 256
+// participants), towards (i).
 #pragma once
 
 #include <stdint.h>
@@ -108,5 +117,27 @@ HGE_NAR_HD bool nar_member_flag(uint32_t mn) { return (mn & 0xFFFFu) == 0 || (mn
 
 // [a >= b] of the four fields in their guard bits (aw with guard bits set, bw without)
 HGE_NAR_HD uint32_t nar_ge4(uint32_t aw, uint32_t bw) { return (aw - bw) & kNarGuard; }
+
+// The staged narrow member rows (one block of npow x npow bytes per round parity), laid
+// out by consuming thread, chunk-major: thread tid = member * tpm + part of a workgroup
+// of bs threads holds the ncw words of columns [part * 4 ncw, (part + 1) * 4 ncw) of its
+// member's row, and loads them vw words at a time; word (k * bs + tid) * vw + s of the
+// block is word k * vw + s of that slice.  Load k of a wave is then one contiguous
+// stretch, and a thread's loads hold bytes of its own member only.
+// cw = column / 4: the word's place in the member's row.
+HGE_NAR_HD int nar_mb_ncw(int bs, int npow) { return npow / 4 / (bs / npow); }
+HGE_NAR_HD int nar_mb_vw(int bs, int npow) {
+  const int ncw = nar_mb_ncw(bs, npow);
+  return ncw % 4 == 0 ? 4 : ncw % 2 == 0 ? 2 : 1;
+}
+HGE_NAR_HD uint32_t nar_mb_word(int bs, int npow, int member, int cw) {
+  const int tpm = bs / npow, ncw = nar_mb_ncw(bs, npow), vw = nar_mb_vw(bs, npow);
+  const int part = cw / ncw, j = cw - part * ncw, k = j / vw;
+  return (uint32_t)((k * bs + member * tpm + part) * vw + (j - k * vw));
+}
+
+// The member row's condition-(ii) flag travels in the hand-off granule: the top bit of
+// its epoch word (epochs stay far below 2^31).
+constexpr uint32_t kNarGranFlag = 0x80000000u;
 
 }  // namespace hge_narrow

@@ -22,6 +22,10 @@
 //     probes, all compares on registers and LDS (no gathers).
 // The strongly-see bits of the selected event against every member (ssc: the
 // vote adjacency k_witness_bits consumes) are one more probe.
+// The narrow widths (HGE_DIR_NARROW_*) run the same search over 8-bit copies of both
+// sides, relative to the previous frontier (hge_narrow.h): the member slice arrives in
+// that form from its producer, the window's first half is encoded after the pick, and
+// the 16-bit slice is loaded only by the rare paths that need it.
 //
 // The frontier hand-off between workgroups is the granule protocol of
 // hge_rounds_coop.hip (8-byte {epoch, value} granules, relaxed agent-scope
@@ -105,10 +109,13 @@ struct DirLDS {
   int sHist[DirGeo<BS, NPOW>::W / 2];  // members by first passing offset (dir_select_pm)
   uint32_t sBits[8];
   // the narrow select's copy: the frontier positions as packed uint16 bases, laid out
-  // like one ring row (part * PS + word), and rows [lo, lo + H) of the ring re-encoded
-  uint32_t sB16[DirGeo<BS, NPOW>::NARROW ? DirGeo<BS, NPOW>::RS : 4] __attribute__((aligned(16)));
+  // like one ring row (part * PS + word), by round parity (sB16[r & 1] = C_r: what round
+  // r encodes against, for round r + 1, while its poll already writes the other one),
+  // and rows [lo, lo + H) of the ring encoded against the previous frontier
+  uint32_t sB16[2][DirGeo<BS, NPOW>::NARROW ? DirGeo<BS, NPOW>::RS : 4] __attribute__((aligned(16)));
   uint32_t sN[DirGeo<BS, NPOW>::NARROW ? DirGeo<BS, NPOW>::H * DirGeo<BS, NPOW>::NRS : 4] __attribute__((aligned(16)));
   int sEx[2];            // per round parity: nonzero = the narrow form is not exact this round
+  int sBig;              // sticky: some frontier position was too large to be a base
   int sFlag[2];          // per round parity: 1 = some member exists, 2 = some chain below stopcut, 4 = hand-off failed
   int s_stamp;          // HGE_STAMPS: thread 0 accumulates probe phases into sdbg
   uint64_t sdbg[2];     // [0] count (LDS reads + VALU), [1] reduce + barrier + read
@@ -259,14 +266,50 @@ __device__ __forceinline__ void dir_members_mb(const uint32_t* mb, uint32_t (&mw
   }
 }
 
+// The narrow slice of the thread from the narrow staging block (hge_narrow.h,
+// nar_mb_word): the same sc1 buffer loads, half the bytes, nothing to encode.
+template <int BS, int NPOW>
+__device__ __forceinline__ void dir_members_nb(const uint32_t* nb, uint32_t (&nw)[DirGeo<BS, NPOW>::NCW]) {
+  using G = DirGeo<BS, NPOW>;
+  constexpr int NVW = G::NVW;
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc((void*)nb, 0, BS * G::NCW * 4, 0x00020000);
+  const int tx = dir_tid();
+#pragma unroll
+  for (int k = 0; k < G::NCW / NVW; k++) {
+    const int off = (k * BS + tx) * NVW * 4;
+    if constexpr (NVW == 4) {
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16);
+      nw[4 * k] = x.x;
+      nw[4 * k + 1] = x.y;
+      nw[4 * k + 2] = x.z;
+      nw[4 * k + 3] = x.w;
+    } else if constexpr (NVW == 2) {
+      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+      const u32x2 x = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 16);
+      nw[2 * k] = x.x;
+      nw[2 * k + 1] = x.y;
+    } else {
+      nw[k] = __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 16);
+    }
+  }
+}
+
 // wave 0 of chain c's workgroup: stage FD[(c, p)] (p = INF32: no member) into MB,
 // read from HBM after the pick.  (Round 3 staged every window row's FD row in LDS
 // ahead of the pick so the stage read LDS: ~10 GB of the kernel's traffic per
 // 256/10M replay for no measured time, 24.57-24.68 vs 24.62-24.69 ms in a
 // same-box A/B, profiles/r04/abfd_*.)
 // Lane l packs columns 4l .. 4l + 3 into row words 2l, 2l + 1 (one part, one chunk).
+// nb != nullptr (the narrow widths): the row also goes out in its 8-bit form, encoded
+// against `bases` (the frontier this workgroup holds in full, L.sB16 of the round that
+// publishes: the next round's base), one word per lane; the even lane of a pair takes
+// its neighbour's word by DPP, so these are 8-byte stores of the same kind.  Returns
+// whether the row breaks condition (ii) (wave-uniform; it travels in the granule).
 template <int BS, int NPOW>
-__device__ __forceinline__ void dir_stage_member(const Tables& t, uint32_t* mb, int c, int p) {
+__device__ __forceinline__ bool dir_stage_member(const Tables& t, uint32_t* mb, uint32_t* nb, const uint32_t* bases,
+                                                 int c, int p) {
   using G = DirGeo<BS, NPOW>;
   constexpr int MVW = G::MVW;
   int lane = threadIdx.x;  // < 64
@@ -274,22 +317,41 @@ __device__ __forceinline__ void dir_stage_member(const Tables& t, uint32_t* mb, 
   // round in one wave, and not kept in registers across the whole round loop)
   asm volatile("" : "+v"(lane));
   const int N = t.N;
-  if (4 * lane < NPOW) {
-    unsigned long long x;
+  const bool act = 4 * lane < NPOW;
+  uint2 a = make_uint2(~0u, ~0u);
+  if (act) {
     if (t.FD16) {  // stored packed already
-      uint2 a = make_uint2(~0u, ~0u);
       if (p != INF32 && 4 * lane < N) a = *(const uint2*)(t.FD16 + rowoff(t, c, p) + 4 * lane);
-      x = (unsigned long long)a.x | ((unsigned long long)a.y << 32);
     } else {
-      int4 a = make_int4(INF32, INF32, INF32, INF32);
-      if (p != INF32 && 4 * lane < N) a = *(const int4*)(t.FD + rowoff(t, c, p) + 4 * lane);
-      x = (unsigned long long)dir_pack_fd(a.x, a.y) | ((unsigned long long)dir_pack_fd(a.z, a.w) << 32);
+      int4 f = make_int4(INF32, INF32, INF32, INF32);
+      if (p != INF32 && 4 * lane < N) f = *(const int4*)(t.FD + rowoff(t, c, p) + 4 * lane);
+      a = make_uint2(dir_pack_fd(f.x, f.y), dir_pack_fd(f.z, f.w));
     }
     const int w = 2 * lane, part = w / G::CW, wp = w - part * G::CW;
     const int k = wp / MVW, sub = wp - k * MVW;
     const size_t word = ((size_t)k * BS + (size_t)c * G::TPM + part) * MVW + sub;
+    const unsigned long long x = (unsigned long long)a.x | ((unsigned long long)a.y << 32);
     __hip_atomic_store((gu64_t*)(mb + word), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  if constexpr (G::NARROW) {
+    if (nb) {
+      uint32_t mn = 0xFFFFFFFFu, word = 0;
+      if (act) {
+        const int w = 2 * lane, part = w / G::CW;
+        const uint2 cb = *(const uint2*)(bases + part * G::PS + (w - part * G::CW));
+        word = hge_narrow::nar_enc_member4(a.x, a.y, cb.x, cb.y, mn);
+      }
+      // every lane of the wave is here: lanes 2m and 2m + 1 are both staging or both idle
+      const uint32_t odd = (uint32_t)__builtin_amdgcn_mov_dpp((int)word, 0xF5, 0xF, 0xF, false);  // quad_perm [1, 1, 3, 3]
+      if (act && (lane & 1) == 0) {
+        const unsigned long long x = (unsigned long long)word | ((unsigned long long)odd << 32);
+        __hip_atomic_store((gu64_t*)(nb + hge_narrow::nar_mb_word(BS, NPOW, c, lane)), x, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      }
+      return __ballot(act && hge_narrow::nar_member_flag(mn)) != 0;
+    }
+  }
+  return false;
 }
 
 // strongly-see count of candidate position p (in the ring) against this
@@ -358,11 +420,12 @@ __device__ __forceinline__ int dir_base_slot(int d) {
   return 2 * (part * G::PS + (w - part * G::CW)) + (d & 1);
 }
 
-// rows [lo, lo + H) of the 16-bit ring re-encoded into L.sN (row k = position lo + k;
-// "no row" entries and columns past N become 0, which passes no member value).
-// Returns the accumulator for nar_window_flag.
+// rows [lo, lo + H) of the 16-bit ring encoded into L.sN against `bases` (row k =
+// position lo + k; "no row" entries and columns past N become 0, which passes no
+// member value).  Returns the accumulator for nar_window_flag.
 template <int BS, int NPOW>
-__device__ __forceinline__ uint32_t dir_encode_window(const Tables& t, DirLDS<BS, NPOW>& L, int lo) {
+__device__ __forceinline__ uint32_t dir_encode_window(const Tables& t, DirLDS<BS, NPOW>& L, const uint32_t* bases,
+                                                      int lo) {
   using G = DirGeo<BS, NPOW>;
   constexpr int GPR = NPOW / 4;  // 4-column groups per row
   uint32_t mx = 0;
@@ -377,7 +440,7 @@ __device__ __forceinline__ uint32_t dir_encode_window(const Tables& t, DirLDS<BS
     uint32_t word = hge_narrow::kNarGuard;
     if (col < t.N) {
       const uint2 la = *(const uint2*)(L.sLA + ((lo + k) & (G::W - 1)) * G::RS + off);
-      const uint2 cb = *(const uint2*)(L.sB16 + off);
+      const uint2 cb = *(const uint2*)(bases + off);
       word = hge_narrow::nar_enc_window4(la.x, la.y, cb.x, cb.y, mx);
     }
     L.sN[k * G::NRS + part * G::NPS + cp / 4] = word;
@@ -385,14 +448,15 @@ __device__ __forceinline__ uint32_t dir_encode_window(const Tables& t, DirLDS<BS
   return mx;
 }
 
-// the thread's 16-bit member slice re-encoded against the bases of its columns;
-// returns the accumulator for nar_member_flag
+// the thread's 16-bit member slice encoded against the bases of its columns (the walk's
+// first round: later rounds' rows are staged encoded, dir_stage_member); returns the
+// accumulator for nar_member_flag
 template <int BS, int NPOW>
-__device__ __forceinline__ uint32_t dir_encode_members(const DirLDS<BS, NPOW>& L, int part,
+__device__ __forceinline__ uint32_t dir_encode_members(const uint32_t* bases, int part,
                                                        const uint32_t (&mw)[DirGeo<BS, NPOW>::CW],
                                                        uint32_t (&nw)[DirGeo<BS, NPOW>::NCW]) {
   using G = DirGeo<BS, NPOW>;
-  const uint32_t* src = L.sB16 + part * G::PS;
+  const uint32_t* src = bases + part * G::PS;
   uint32_t mn = 0xFFFFFFFFu;
 #pragma unroll
   for (int k0 = 0; k0 < G::CW; k0 += G::VW) {
@@ -457,8 +521,8 @@ __device__ __forceinline__ int dir_count_n(const DirLDS<BS, NPOW>& L, int k, int
   return cnt;
 }
 
-// The 16-bit member slice of round r again, for the paths that need it after the
-// narrow encode consumed it (the exact select, dir_probe_search): from MB[r & 1],
+// The 16-bit member slice of round r, for the paths that need it (the exact select,
+// dir_probe_search, a kept frontier row outside the narrow rows): from MB[r & 1],
 // which no producer writes before this workgroup has published round r + 1, or in
 // the walk's first round from the FD table.  Call it before the round's publish.
 template <int BS, int NPOW>
@@ -663,7 +727,7 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
                                                       int32_t* err, uint64_t* ssc, uint32_t* mbuf,
                                                       uint64_t* dbg, const int32_t* start, int32_t* hist,
                                                       int hmax, const int32_t* stopcut, int extra, int stall_ep,
-                                                      int force_exact, unsigned long long* paths,
+                                                      int force_exact, int mflag_ep, unsigned long long* paths,
                                                       unsigned long long* paths_next) {
   // History mode (hist != nullptr; a walker of the cross-GPU split, babble_amd/dist.py):
   // the walk starts at the frontier `start` (rlo = 0, Rprev = 0), writes frontier
@@ -675,6 +739,9 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
   // does not publish and every workgroup gives up at once, as on a timed-out poll, so
   // the other chains' rows of that round are written and chain 0's is not.
   // force_exact (tests, HGE_TEST_DIR_EXACT): every round takes the 16-bit select.
+  // mflag_ep > 0 (tests, HGE_TEST_DIR_MEMBER_FLAG): at hand-off epoch mflag_ep chain 1
+  // raises its staged row's condition-(ii) flag although the row is fine: the round
+  // that consumes it takes the 16-bit select on every chain, with the same result.
   // paths[0], paths[1] += this chain's rounds selected over the narrow rows / by the
   // 16-bit select (one add per workgroup, at exit); chain 0 clears paths_next[0..1], the
   // counters of the next walk on the stream.
@@ -706,6 +773,12 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
   const int lenc = len[c];
   gu64_t* gr[2] = {(gu64_t*)gran, (gu64_t*)(gran + N)};
   uint32_t* mbp[2] = {mbuf, mbuf + (size_t)NPOW * G::MBW};
+  // the narrow blocks (NPOW x NPOW bytes each) lie behind the two 16-bit ones
+  uint32_t* nbp[2] = {nullptr, nullptr};
+  if constexpr (G::NARROW) {
+    nbp[0] = mbuf + 2 * (size_t)NPOW * G::MBW;
+    nbp[1] = nbp[0] + (size_t)NPOW * NPOW / 4;
+  }
   if (tid < N) {
     int P;
     if (hist) {
@@ -719,16 +792,25 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
     L.sP[tid] = P;
   }
   if constexpr (G::NARROW) {  // every column's base (columns past N: 0, their member values are unset)
-    if (tid < NPOW) ((uint16_t*)L.sB16)[dir_base_slot<BS, NPOW>(tid)] = tid < N ? (uint16_t)hge_narrow::nar_base16(L.sP[tid]) : 0;
+    // (both parities: columns past N are never written again)
+    if (tid < NPOW) {
+      const uint16_t b = tid < N ? (uint16_t)hge_narrow::nar_base16(L.sP[tid]) : 0;
+      ((uint16_t*)L.sB16[0])[dir_base_slot<BS, NPOW>(tid)] = b;
+      ((uint16_t*)L.sB16[1])[dir_base_slot<BS, NPOW>(tid)] = b;
+    }
   }
   if (tid == 0) {
     L.s_stamp = stamping ? 1 : 0;
     L.sdbg[0] = L.sdbg[1] = 0;
     L.sEx[0] = L.sEx[1] = 0;
+    L.sBig = 0;
   }
   __syncthreads();
   if constexpr (G::NARROW) {
-    if (tid < N && hge_narrow::nar_base_too_large(L.sP[tid])) atomicOr(&L.sEx[rlo & 1], 1);
+    if (tid < N && hge_narrow::nar_base_too_large(L.sP[tid])) {
+      L.sEx[rlo & 1] = 1;
+      L.sBig = 1;
+    }
   }
   int n_nar = 0, n_ex = 0;  // this chain's rounds by select path
   const int rcap = hist ? hmax : t.Rcap;
@@ -738,10 +820,31 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
   dir_load<BS, NPOW>(t, L, c, lo, DirGeo<BS, NPOW>::W, lenc, pv);
   int f0 = INF32, fn = 0;  // rows fetched for the next round: [f0, f0 + fn)
   // members of the first round from the FD table; later rounds' members are loaded
-  // by each wave right after its own poll of the previous round (below)
-  uint32_t mw[G::CW];
-  dir_members_fd<BS, NPOW>(t, d, part, d < N ? L.sP[d] : INF32, mw);
-  if constexpr (G::NARROW) __syncthreads();  // the first window is stored: the round's top re-encodes it
+  // by each wave right after its own poll of the previous round (below).  The narrow
+  // widths keep the 8-bit slice nw across the loop and form the 16-bit one only where a
+  // rare path needs it; the others keep the 16-bit slice mw.
+  uint32_t mw[G::NARROW ? 1 : G::CW];
+  uint32_t nw[G::NARROW ? G::NCW : 1];
+  // nar: L.sN holds rows [lo, lo + H) encoded against this round's bases (block-uniform)
+  bool nar = false;
+  if constexpr (G::NARROW) {
+    // the first round's base is its own frontier: window and members are encoded here
+    __syncthreads();  // the first window is stored
+    nar = lo != INF32 && lo < lenc && !force_exact;
+    if (nar) {
+      uint32_t m16[G::CW];
+      dir_members_fd<BS, NPOW>(t, d, part, d < N ? L.sP[d] : INF32, m16);
+      if (d >= N) {
+#pragma unroll
+        for (int k = 0; k < G::CW; k++) m16[k] = 0xFFFFFFFFu;
+      }
+      const uint32_t mx = dir_encode_window<BS, NPOW>(t, L, L.sB16[rlo & 1], lo);
+      const uint32_t mn = dir_encode_members<BS, NPOW>(L.sB16[rlo & 1], part, m16, nw);
+      if (hge_narrow::nar_window_flag(mx) || hge_narrow::nar_member_flag(mn)) L.sEx[rlo & 1] = 1;
+    }
+  } else {
+    dir_members_fd<BS, NPOW>(t, d, part, d < N ? L.sP[d] : INF32, mw);
+  }
   for (int r = rlo;; r++) {
     if (r + 1 >= rcap) {
       if (c == 0 && tid == 0) {
@@ -751,34 +854,33 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
       break;
     }
     DSTAMP_START
-    if (d >= N) {
+    if constexpr (G::NARROW) {
+      if (d >= N) {  // no member: 127 in every field, which no window value reaches
 #pragma unroll
-      for (int k = 0; k < G::CW; k++) mw[k] = 0xFFFFFFFFu;
+        for (int k = 0; k < G::NCW; k++) nw[k] = 0x7F7F7F7Fu;
+      }
+    } else {
+      if (d >= N) {
+#pragma unroll
+        for (int k = 0; k < G::CW; k++) mw[k] = 0xFFFFFFFFu;
+      }
     }
     if (tid < DIR_MAXP) L.sCnt[tid] = 0;
     if (tid < 8) L.sBits[tid] = 0;
     if (tid < DirGeo<BS, NPOW>::W / 2) L.sHist[tid] = 0;
     if (tid == 0) {
       L.sFlag[(r + 1) & 1] = 0;  // read after the previous round's poll barrier
-      L.sEx[(r + 1) & 1] = 0;    // (set from that barrier on, read after the next round's first one)
+      // (set from this round's first barrier on, read after the next round's first one;
+      // round r + 1 encodes against C_r: too large a base there is known since the last
+      // poll, and stays)
+      L.sEx[(r + 1) & 1] = L.sBig;
     }
     const int Pc = L.sP[c];
     const int cur = (r + 1 < Rprev) ? t.C[(size_t)(r + 1) * N + c] : INF32;
-    // A round that selects re-encodes its window's first half and the member slice
-    // relative to the frontier (complete since the poll barrier: L.sP, L.sB16, and the
-    // window rows were stored before it), so the barrier below also publishes L.sN.
-    // mw is spent by this: what needs the 16-bit slice afterwards reloads it.
-    uint32_t nw[G::NCW];
-    bool enc = false;
-    if constexpr (G::NARROW) {
-      enc = Pc != INF32 && cur == INF32 && lo != INF32 && lo < lenc && !force_exact;
-      if (enc) {  // block-uniform
-        const uint32_t mx = dir_encode_window<BS, NPOW>(t, L, lo);
-        const uint32_t mn = dir_encode_members<BS, NPOW>(L, part, mw, nw);
-        if (hge_narrow::nar_window_flag(mx) || hge_narrow::nar_member_flag(mn)) L.sEx[r & 1] = 1;
-      }
-    }
-    __syncthreads();  // window stored, counters clear
+    // The narrow rows of this round were written before the poll barrier (the window by
+    // this workgroup after its pick, the member slice by its producers), both against
+    // the previous frontier: nothing is encoded here.
+    __syncthreads();  // counters clear
     DSTAMP(0);
     int slot = 0;
     int nxt = INF32;
@@ -790,12 +892,15 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
       DSTAMP(1);
       if (stamping) st_acc[6] += slot;
       if (tid < 64 && !(stall && c == 0)) {
-        dir_stage_member<BS, NPOW>(t, mbp[(r + 1) & 1], c, nxt);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // (the narrow row against C_r, this round's L.sB16: the next round's base)
+        bool mflag = dir_stage_member<BS, NPOW>(t, mbp[(r + 1) & 1], nbp[(r + 1) & 1], L.sB16[r & 1], c, nxt);
+        if (mflag_ep > 0 && c == 1 && r - rlo + 1 == mflag_ep) mflag = true;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // both blocks' stores
         if (tid == 0) {
           if (hist) hist[(size_t)(r + 1) * N + c] = nxt;
           else if (nxt != INF32 && cur == INF32) t.C[(size_t)(r + 1) * N + c] = nxt;
-          const uint64_t g = ((uint64_t)(uint32_t)(r - rlo + 1) << 32) | (uint32_t)nxt;
+          const uint32_t epw = (uint32_t)(r - rlo + 1) | (mflag ? hge_narrow::kNarGranFlag : 0u);
+          const uint64_t g = ((uint64_t)epw << 32) | (uint32_t)nxt;
           __hip_atomic_store(gr[(r + 1) & 1] + c, (unsigned long long)g, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -804,28 +909,51 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
     if (Pc == INF32) {
       publish();
     } else if (cur != INF32) {
-      // a frontier row kept from an earlier batch: no select (mw is still the 16-bit
-      // slice), one probe for its strongly-see bits
+      // a frontier row kept from an earlier batch: no select, one count for its
+      // strongly-see bits
       nxt = cur;
-      publish();
-      if (nxt < lo || nxt >= lo + DirGeo<BS, NPOW>::W) {
-        __syncthreads();
-        lo = nxt;
-        dir_load<BS, NPOW>(t, L, c, lo, DirGeo<BS, NPOW>::W, lenc, pv);
-        __syncthreads();
+      if constexpr (G::NARROW) {
+        // over the narrow rows when the row is among them and the round is unflagged;
+        // otherwise over the 16-bit slice, loaded before the publish (dir_members_reload)
+        if (nar && L.sEx[r & 1] == 0 && nxt >= lo && nxt - lo < G::H) {  // block-uniform
+          publish();
+          pb = dir_count_n<BS, NPOW>(L, nxt - lo, part, nw) >= t.SM;
+        } else {
+          uint32_t m16[G::CW];
+          dir_members_reload<BS, NPOW>(t, L, mbp[r & 1], r == rlo, d, part, m16);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the slice is in registers
+          __syncthreads();                                  // ... of every wave, before wave 0 publishes
+          publish();
+          if (nxt < lo || nxt >= lo + DirGeo<BS, NPOW>::W) {
+            __syncthreads();
+            lo = nxt;
+            dir_load<BS, NPOW>(t, L, c, lo, DirGeo<BS, NPOW>::W, lenc, pv);
+            __syncthreads();
+          }
+          pb = dir_count<BS, NPOW>(L, nxt, part, m16) >= t.SM;
+        }
+      } else {
+        publish();
+        if (nxt < lo || nxt >= lo + DirGeo<BS, NPOW>::W) {
+          __syncthreads();
+          lo = nxt;
+          dir_load<BS, NPOW>(t, L, c, lo, DirGeo<BS, NPOW>::W, lenc, pv);
+          __syncthreads();
+        }
+        pb = dir_count<BS, NPOW>(L, nxt, part, mw) >= t.SM;
       }
-      pb = dir_count<BS, NPOW>(L, nxt, part, mw) >= t.SM;
     } else {
       int s;
       if constexpr (G::NARROW) {
         const uint32_t* mbr = mbp[r & 1];
-        if (enc && L.sEx[r & 1] == 0) {
+        if (nar && L.sEx[r & 1] == 0) {
           n_nar++;
           s = dir_select<BS, NPOW, true>(t, c, lenc, L, d, part, nw, slot, pv, lo, pb, mbr, r == rlo);
         } else {  // a round whose narrow form is not exact, or the test hook
           n_ex++;
-          dir_members_reload<BS, NPOW>(t, L, mbr, r == rlo, d, part, mw);
-          s = dir_select<BS, NPOW, false>(t, c, lenc, L, d, part, mw, slot, pv, lo, pb, mbr, r == rlo);
+          uint32_t m16[G::CW];
+          dir_members_reload<BS, NPOW>(t, L, mbr, r == rlo, d, part, m16);
+          s = dir_select<BS, NPOW, false>(t, c, lenc, L, d, part, m16, slot, pv, lo, pb, mbr, r == rlo);
         }
       } else {
         n_ex++;
@@ -853,13 +981,36 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
       f0 = (lo != INF32 && nxt < lo + DirGeo<BS, NPOW>::W) ? lo + DirGeo<BS, NPOW>::W : nxt;
       fn = nxt + DirGeo<BS, NPOW>::W - f0;
     }
+    // The next round's narrow window, rows [nxt, nxt + H) against C_r (its base): every
+    // wave is done with this round's L.sN since the strongly-see barrier, and the rows
+    // are in the ring already unless the window outruns it (rare: then behind the
+    // stores and one barrier).  Encoded while the fetch is in flight; sets condition
+    // (i)'s flag of the next round.
+    bool late = false;
+    if constexpr (G::NARROW) {
+      nar = nxt != INF32 && !force_exact;
+      late = nar && fn > DirGeo<BS, NPOW>::W - G::H;  // nxt + H > (the ring's end) = f0
+    }
     lo = nxt;
     dir_fetch<BS, NPOW>(t, c, f0, fn, lenc, pv);
+    if constexpr (G::NARROW) {
+      if (nar && !late) {
+        const uint32_t mx = dir_encode_window<BS, NPOW>(t, L, L.sB16[r & 1], nxt);
+        if (hge_narrow::nar_window_flag(mx)) L.sEx[(r + 1) & 1] = 1;
+      }
+    }
     dir_store<BS, NPOW>(t, L, f0, fn, lenc, pv);
     if (fn > DIR_CH) {  // rare: the LA rows past the first chunk (the FD rows are in flight)
       for (int q = DIR_CH; q < fn; q += DIR_CH) {
         dir_fetch<BS, NPOW>(t, c, f0 + q, fn - q, lenc, pv);
         dir_store<BS, NPOW>(t, L, f0 + q, fn - q, lenc, pv);
+      }
+    }
+    if constexpr (G::NARROW) {
+      if (late) {  // block-uniform
+        __syncthreads();  // the rows past the old ring are stored
+        const uint32_t mx = dir_encode_window<BS, NPOW>(t, L, L.sB16[r & 1], nxt);
+        if (hge_narrow::nar_window_flag(mx)) L.sEx[(r + 1) & 1] = 1;
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's FD rows have landed
@@ -876,13 +1027,18 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
       const unsigned ep = (unsigned)(r - rlo + 1);
       const gu64_t* g = gr[(r + 1) & 1];
       unsigned spins = 0;
-      bool fail = false;
+      bool fail = false, mflag = false;
       int P = INF32;
       for (;;) {
         bool ok = true;
         if (d < N) {
           const unsigned long long x = __hip_atomic_load(g + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = (unsigned)(x >> 32) == ep;
+          if constexpr (G::NARROW) {  // the epoch word's top bit: the staged row breaks condition (ii)
+            ok = ((unsigned)(x >> 32) & ~hge_narrow::kNarGranFlag) == ep;
+            mflag = ((unsigned)(x >> 32) & hge_narrow::kNarGranFlag) != 0;
+          } else {
+            ok = (unsigned)(x >> 32) == ep;
+          }
           P = (int)(uint32_t)x;
         }
         if (__all(ok)) break;
@@ -895,11 +1051,16 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       if (part == 0 && d < N) {
         L.sP[d] = P;
-        if constexpr (G::NARROW) ((uint16_t*)L.sB16)[dir_base_slot<BS, NPOW>(d)] = (uint16_t)hge_narrow::nar_base16(P);
+        // (the other parity: waves of this workgroup may still encode against C_r)
+        if constexpr (G::NARROW)
+          ((uint16_t*)L.sB16[(r + 1) & 1])[dir_base_slot<BS, NPOW>(d)] = (uint16_t)hge_narrow::nar_base16(P);
       }
-      if constexpr (G::NARROW) {  // a base the narrow form cannot take: the next round selects in 16 bits
+      if constexpr (G::NARROW) {
+        // a member row that breaks condition (ii): the next round selects in 16 bits;
+        // a base the narrow form cannot take: every round from the one after it on
+        if (__ballot(d < N && mflag) != 0 && (threadIdx.x & 63) == 0) L.sEx[(r + 1) & 1] = 1;
         if (__ballot(part == 0 && d < N && hge_narrow::nar_base_too_large(P)) != 0 && (threadIdx.x & 63) == 0)
-          L.sEx[(r + 1) & 1] = 1;
+          L.sBig = 1;
       }
       const bool any = __ballot(d < N && P != INF32) != 0;
       const bool notpast = stopcut && __ballot(part == 0 && d < N && P < stopcut[d]) != 0;  // INF32 passes
@@ -909,11 +1070,20 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
         atomicOr(err, 1);
         atomicOr(rstate + 1, 4);  // the downstream kernels stand down, as on overflow
       }
-      if (!fail) {
-        dir_members_mb<BS, NPOW>(mbp[(r + 1) & 1], mw);
-      } else {  // (the walk ends below: no round reads the slice again, so it need not stay in registers)
+      if constexpr (G::NARROW) {
+        if (!fail) {
+          dir_members_nb<BS, NPOW>(nbp[(r + 1) & 1], nw);
+        } else {  // (the walk ends below: no round reads the slice again, so it need not stay in registers)
 #pragma unroll
-        for (int k = 0; k < G::CW; k++) mw[k] = 0;
+          for (int k = 0; k < G::NCW; k++) nw[k] = 0;
+        }
+      } else {
+        if (!fail) {
+          dir_members_mb<BS, NPOW>(mbp[(r + 1) & 1], mw);
+        } else {
+#pragma unroll
+          for (int k = 0; k < G::CW; k++) mw[k] = 0;
+        }
       }
     }
     __syncthreads();  // every wave has polled (and stored its window rows)
@@ -950,10 +1120,10 @@ __global__ void __launch_bounds__(BS, 4) k_rounds_direct(Tables t, const int32_t
 }
 
 template __global__ void k_rounds_direct<1024, 64>(Tables, const int32_t*, const int32_t*, int32_t*, int, const int32_t*, int,
-    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, unsigned long long*, unsigned long long*);
+    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, int, unsigned long long*, unsigned long long*);
 template __global__ void k_rounds_direct<1024, 128>(Tables, const int32_t*, const int32_t*, int32_t*, int, const int32_t*, int,
-    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, unsigned long long*, unsigned long long*);
+    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, int, unsigned long long*, unsigned long long*);
 template __global__ void k_rounds_direct<1024, 256>(Tables, const int32_t*, const int32_t*, int32_t*, int, const int32_t*, int,
-    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, unsigned long long*, unsigned long long*);
+    uint64_t*, int32_t*, uint64_t*, uint32_t*, uint64_t*, const int32_t*, int32_t*, int, const int32_t*, int, int, int, int, unsigned long long*, unsigned long long*);
 
 }  // namespace hge
