@@ -33,6 +33,12 @@
 //                 ConsensusSorter sort of the call's batch (consensus_sorter.go:36-59,
 //                 PRN = 0) in LDS.
 //
+// Opt-in (hge_batch_set_delivery): the kernels that write the order (kb_sort,
+// kb_consensus) write it, the per-call batch sizes and, in their DLV instances, the
+// ordered events' round received and consensus timestamp into mapped pinned host
+// memory, so a run ends with every graph's commit stream on the host
+// (tests/test_gpu_batch_commit.py).
+//
 // Everything on the path is integer; results are bit-exact with the oracle
 // (tests/test_gpu_batch.py, tests/test_gpu_mc.py: every graph's full-state digest).
 #include <hip/hip_runtime.h>
@@ -88,6 +94,9 @@ struct BT {
   int32_t *rcnt, *ver, *thv;   // [ro + r] events in the round so far, fame/witness version, theta's version
   int32_t* th;                 // [ro + r][N] receive thresholds
   int32_t *U, *Ur, *Ucp;       // [eo + k] undetermined list past LDS: id, round, creator << 24 | index
+  // The commit stream (with ord_rr / ord_cts at the end).  Store-only: with delivery on
+  // (hge_batch_set_delivery) these point into mapped host memory, so no kernel may
+  // load from them.
   int32_t* order;              // [eo + k] consensus order
   int64_t* counts;             // [co + c] batch size of call c
   int64_t* scal;               // [g][8] R, LCR, LCRE, transactions, ordered, undetermined, error
@@ -120,6 +129,13 @@ struct BT {
   int32_t* wlc;          // their count
   int64_t* gctx;         // [g] ConsensusTransactions
   int2* cinf;            // [eo + x] kb_levels' records for kb_coords
+  // The commit stream's records beside `order` (store-only like it; null: not delivered).
+  // Only the DLV instances of kb_sort and kb_consensus touch them: as a run-time pointer
+  // test the extra stores cost kb_sort<256, 0, 1024> a wave per SIMD and
+  // kb_consensus<32, 4> scratch (profiles/batch_commit/resource_usage.txt).  Last, so
+  // that every other field keeps its offset in the kernels' arguments.
+  int32_t* ord_rr;       // [eo + k] round received of order[eo + k]
+  int64_t* ord_cts;      // [eo + k] its consensus timestamp
 };
 
 __device__ __forceinline__ int rl(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
@@ -884,7 +900,7 @@ __device__ __forceinline__ void sort_regs(int64_t (&v)[M]) {
 // OCC: workgroups per CU the register budget is sized for.  One graph per CU
 // leaves the compiler its 230 VGPRs; with more graphs than two per CU, 4 per CU
 // (128 VGPRs, a few spills) take the whole batch in one pass.
-template <int NM, int OCC>
+template <int NM, int OCC, bool DLV>
 __global__ __launch_bounds__(256, OCC) void kb_consensus(BT t) {
   // KB: the LDS sort's capacity, a power of two (the network pads to one)
   constexpr int NWV = 4, RW = 8, UL = 1536, KB = 1024, CPW = 2, NCH = NWV * CPW, SPAN = 64 * NCH;
@@ -1383,6 +1399,11 @@ __global__ __launch_bounds__(256, OCC) void kb_consensus(BT t) {
         sort_keys_lds(t, eo, nb, kri, kc, ks);
         __syncthreads();
         for (int p = tid; p < nb; p += NT) t.order[eo + nord + p] = (int32_t)(kri[p] & 0xFFFFu);
+        if (DLV)  // the commit records beside the ids
+          for (int p = tid; p < nb; p += NT) {
+            t.ord_rr[eo + nord + p] = (int32_t)(kri[p] >> 16);
+            t.ord_cts[eo + nord + p] = kc[p];
+          }
       } else {
         // past KB keys: the same network on the graph's global scratch (2E entries
         // from 2 eo: nord + the padded size stays below 2E); the first KB keys are in LDS
@@ -1399,6 +1420,11 @@ __global__ __launch_bounds__(256, OCC) void kb_consensus(BT t) {
         sort_keys_g(t, eo, nb, t.krr + so, t.kct + so, t.ks0 + so, t.kid + so);
         __syncthreads();
         for (int p = tid; p < nb; p += NT) t.order[eo + nord + p] = ld(&t.kid[so + p]);
+        if (DLV)
+          for (int p = tid; p < nb; p += NT) {
+            t.ord_rr[eo + nord + p] = ld(&t.krr[so + p]);
+            t.ord_cts[eo + nord + p] = ld(&t.kct[so + p]);
+          }
       }
     }
     if (tid == 0) t.counts[d.co + c] = nb;
@@ -1464,6 +1490,47 @@ struct Buf {
   }
 };
 
+// A host array of the commit stream: mapped pinned memory the kernels store to
+// (dev: its device-side address), or pageable memory that a copy fills after the run
+// when the pinned allocation fails.
+template <typename T>
+struct HostField {
+  T* h = nullptr;
+  T* dev = nullptr;
+  size_t cap = 0;
+  bool pinned = false;
+  void need(size_t n, bool try_pin) {
+    if (h && n <= cap) return;
+    free_();
+    n = std::max<size_t>(n, 1);
+    if (try_pin) {
+      void *p = nullptr, *dp = nullptr;
+      if (hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) == hipSuccess) {
+        if (hipHostGetDevicePointer(&dp, p, 0) == hipSuccess && dp) {
+          h = (T*)p;
+          dev = (T*)dp;
+          pinned = true;
+        } else {
+          (void)hipHostFree(p);
+        }
+      }
+      if (!h) (void)hipGetLastError();  // not an error of the run: the copy path takes over
+    }
+    if (!h) {
+      h = (T*)malloc(n * sizeof(T));
+      if (!h) throw BatchError{HGE_ERR_INTERNAL, "commit stream: host allocation failed"};
+    }
+    cap = n;
+  }
+  void free_() {
+    if (h && pinned) (void)hipHostFree(h);
+    else free(h);
+    h = dev = nullptr;
+    cap = 0;
+    pinned = false;
+  }
+};
+
 }  // namespace
 
 struct hge_batch {
@@ -1511,9 +1578,46 @@ struct hge_batch {
   Buf<int64_t> d_gctx, d_ctsch;
   int Emax = 0;
   int64_t n_fallback = 0;  // graphs the last run replayed through kb_consensus
+  // the commit stream in host memory (hge_batch_set_delivery), pooled like the device
+  // tables: ids / rr / cts at GDesc::eo, counts at GDesc::co
+  uint32_t deliver = 0;   // requested: bit 0 order and counts, bit 1 rr and cts as well
+  int32_t delivered = 0;  // the last run: 0 not delivered, 1 written by the kernels, 2 copied after the run
+  uint32_t delivered_what = 0;
+  bool no_pin = getenv("HGB_TEST_NO_PIN") != nullptr;  // test hook: take the copy path
+  HostField<int32_t> h_ids, h_orr;
+  HostField<int64_t> h_octs, h_counts;
+  Buf<int32_t> d_orr;  // the copy path's device side of rr / cts (ids and counts: d_order, d_counts)
+  Buf<int64_t> d_octs;
+
+  // sized from the staged pools; kept across runs
+  void ensure_delivery() {
+    if (!(deliver & 1)) return;
+    const size_t E1 = (size_t)std::max<int64_t>(Etot, 1), K1 = (size_t)std::max<int64_t>(Ktot, 1);
+    h_ids.need(E1, !no_pin);
+    h_counts.need(K1, !no_pin);
+    bool pin = h_ids.pinned && h_counts.pinned;
+    if (deliver & 2) {
+      h_orr.need(E1, !no_pin);
+      h_octs.need(E1, !no_pin);
+      pin = pin && h_orr.pinned && h_octs.pinned;
+      if (!pin) {
+        d_orr.need(E1);
+        d_octs.need(E1);
+      }
+    }
+  }
+  bool delivery_pinned() const {
+    return h_ids.pinned && h_counts.pinned && (!(deliver & 2) || (h_orr.pinned && h_octs.pinned));
+  }
 
   void free_all() {
     d_gd.free_();
+    h_ids.free_();
+    h_orr.free_();
+    h_octs.free_();
+    h_counts.free_();
+    d_orr.free_();
+    d_octs.free_();
     for (auto* b : {&d_cr, &d_ix, &d_sp, &d_op, &d_oc, &d_ntx, &d_clen, &d_chain, &d_LA, &d_FDT, &d_FD, &d_round,
                     &d_rr, &d_W, &d_WIX, &d_WFD, &d_rcnt, &d_ver, &d_thv, &d_th, &d_U, &d_Ur, &d_Ucp, &d_order,
                     &d_krr, &d_kid})
@@ -1604,7 +1708,10 @@ struct hge_batch {
   }
 
   void stage() {
-    if (staged) return;
+    if (staged) {
+      ensure_delivery();
+      return;
+    }
     BCHK(hipSetDevice(device));
     const int G = (int)gs.size();
     hd.assign(G, GDesc{});
@@ -1739,6 +1846,7 @@ struct hge_batch {
     d_gctx.need(G);
     d_cinf.need(E1);
     BCHK(hipStreamSynchronize(st));
+    ensure_delivery();
     staged = true;
   }
 
@@ -1786,6 +1894,8 @@ struct hge_batch {
     t.Ucp = d_Ucp.p;
     t.order = d_order.p;
     t.counts = d_counts.p;
+    t.ord_rr = nullptr;
+    t.ord_cts = nullptr;
     t.scal = d_scal.p;
     t.krr = d_krr.p;
     t.kct = d_kct.p;
@@ -1829,7 +1939,7 @@ struct hge_batch {
     if (e != hipSuccess) throw BatchError{HGE_ERR_DEVICE, std::string("batch launch: ") + hipGetErrorString(e)};
   }
 
-  template <int NM>
+  template <int NM, bool DLV>
   void run_stages(int G, const BT& t) {
     // a workgroup of 1,024 threads per graph while two fit a CU, else 512
     // 1,024 threads per graph and the kb_levels pass while two graphs fit a CU, else
@@ -1881,16 +1991,17 @@ struct hge_batch {
     // call buckets: up to 1,024 keys one wave each (a workgroup of four while the
     // batch has few buckets), larger ones a workgroup each
     const int nbk = (int)std::min<int64_t>(std::max<int64_t>(Ktot, 1), (int64_t)ncu * 16);
-    if (Ktot > 16 * (int64_t)ncu) hipLaunchKernelGGL((kb_sort<64, 0, 1024>), dim3(nbk), dim3(64), 0, st, t, 0);
-    else hipLaunchKernelGGL((kb_sort<256, 0, 1024>), dim3(nbk), dim3(256), 0, st, t, 0);
+    if (Ktot > 16 * (int64_t)ncu) hipLaunchKernelGGL((kb_sort<64, 0, 1024, DLV>), dim3(nbk), dim3(64), 0, st, t, 0);
+    else hipLaunchKernelGGL((kb_sort<256, 0, 1024, DLV>), dim3(nbk), dim3(256), 0, st, t, 0);
     BCHK(hipGetLastError());
-    hipLaunchKernelGGL((kb_sort<256, 1024, 4096>), dim3(ncu), dim3(256), 0, st, t, 1);
+    hipLaunchKernelGGL((kb_sort<256, 1024, 4096, DLV>), dim3(ncu), dim3(256), 0, st, t, 1);
     BCHK(hipGetLastError());
     BCHK(hipEventRecord(ev[8], st));
   }
 
   int64_t run() {
     stage();
+    delivered = 0;
     const int G = (int)gs.size();
     if (G == 0) return 0;
     const size_t RN = (size_t)std::max<int64_t>(Rtot, 1) * N;
@@ -1915,9 +2026,22 @@ struct hge_batch {
     hipLaunchKernelGGL(kb_clear, dim3((unsigned)std::min<size_t>(2048, (E1 * 8 / 16 + 255) / 256 + 1)), dim3(256), 0, st, cl);
     BCHK(hipGetLastError());
     BT t = tables();
+    // delivery: the sorts and kb_consensus store the commit stream into mapped host
+    // memory (the fallback pass below into the same slots); it is the host's after the
+    // run's last synchronise
+    const int mode = !(deliver & 1) ? 0 : delivery_pinned() ? 1 : 2;
+    if (mode == 1) {
+      t.order = h_ids.dev;
+      t.counts = h_counts.dev;
+    }
+    if (mode && (deliver & 2)) {
+      t.ord_rr = mode == 1 ? h_orr.dev : d_orr.p;
+      t.ord_cts = mode == 1 ? h_octs.dev : d_octs.p;
+    }
     BCHK(hipEventRecord(ev[0], st));
-    if (N <= 32) run_stages<32>(G, t);
-    else run_stages<64>(G, t);
+    const bool dlv = t.ord_rr != nullptr;  // the kernel instances that store rr / cts in commit order
+    if (N <= 32) dlv ? run_stages<32, true>(G, t) : run_stages<32, false>(G, t);
+    else dlv ? run_stages<64, true>(G, t) : run_stages<64, false>(G, t);
     h_scal.resize((size_t)G * 8);
     BCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
     BCHK(hipStreamSynchronize(st));
@@ -1933,12 +2057,15 @@ struct hge_batch {
       const int F = (int)fb.size();
       float ms = 0;
       BCHK(hipEventRecord(ev[7], st));
+      auto replay = [&](auto kern_off, auto kern_on) {
+        dlv ? launch(kern_on, F, t, 256) : launch(kern_off, F, t, 256);
+      };
       if (N <= 32) {
-        if (F > 2 * ncu) launch(kb_consensus<32, 4>, F, t, 256);
-        else launch(kb_consensus<32, 1>, F, t, 256);
+        if (F > 2 * ncu) replay(kb_consensus<32, 4, false>, kb_consensus<32, 4, true>);
+        else replay(kb_consensus<32, 1, false>, kb_consensus<32, 1, true>);
       } else {
-        if (F > 2 * ncu) launch(kb_consensus<64, 4>, F, t, 256);
-        else launch(kb_consensus<64, 1>, F, t, 256);
+        if (F > 2 * ncu) replay(kb_consensus<64, 4, false>, kb_consensus<64, 4, true>);
+        else replay(kb_consensus<64, 1, false>, kb_consensus<64, 1, true>);
       }
       BCHK(hipEventRecord(ev[8], st));
       BCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
@@ -1961,6 +2088,16 @@ struct hge_batch {
         throw BatchError{HGE_ERR_INTERNAL, "batch graph " + std::to_string(g) + ": round capacity exceeded"};
       tot += h_scal[(size_t)g * 8 + 4];
     }
+    if (mode == 2) {  // no pinned memory: one pooled copy per field
+      BCHK(hipMemcpy(h_ids.h, d_order.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
+      BCHK(hipMemcpy(h_counts.h, d_counts.p, (size_t)Ktot * 8, hipMemcpyDeviceToHost));
+      if (deliver & 2) {
+        BCHK(hipMemcpy(h_orr.h, d_orr.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
+        BCHK(hipMemcpy(h_octs.h, d_octs.p, (size_t)Etot * 8, hipMemcpyDeviceToHost));
+      }
+    }
+    delivered = mode;
+    delivered_what = deliver;
     ran = true;
     return tot;
   }
@@ -2068,8 +2205,13 @@ int hge_batch_results(hge_batch* b, int32_t g, int32_t* order, int64_t* counts, 
   const GDesc& d = b->hd[g];
   const int64_t* s = &b->h_scal[(size_t)g * 8];
   const int N = b->N;
-  b->down(order, b->d_order.p + d.eo, (size_t)s[4]);
-  b->down(counts, b->d_counts.p + d.co, (size_t)d.K);
+  if (b->delivered) {  // the last run delivered them: they are in host memory already
+    if (order && s[4]) memcpy(order, b->h_ids.h + d.eo, (size_t)s[4] * sizeof(int32_t));
+    if (counts && d.K) memcpy(counts, b->h_counts.h + d.co, (size_t)d.K * sizeof(int64_t));
+  } else {
+    b->down(order, b->d_order.p + d.eo, (size_t)s[4]);
+    b->down(counts, b->d_counts.p + d.co, (size_t)d.K);
+  }
   b->down(round, b->d_round.p + d.eo, (size_t)d.E);
   b->down(witness, b->d_wit.p + d.eo, (size_t)d.E);
   b->down(rr, b->d_rr.p + d.eo, (size_t)d.E);
@@ -2088,6 +2230,35 @@ int hge_batch_results(hge_batch* b, int32_t g, int32_t* order, int64_t* counts, 
 }
 
 int64_t hge_batch_fallbacks(hge_batch* b) { return b ? b->n_fallback : -1; }
+
+int hge_batch_set_delivery(hge_batch* b, uint32_t what) {
+  if (!b) return HGE_ERR_ARG;
+  if (what > 3 || what == 2) {
+    b->err = "hge_batch_set_delivery: what is 0, 1 or 3 (bit 1 needs bit 0)";
+    return HGE_ERR_ARG;
+  }
+  b->deliver = what;
+  return HGE_OK;
+}
+
+int32_t hge_batch_delivery(hge_batch* b) { return b && b->ran ? b->delivered : 0; }
+
+int hge_batch_commits_view(hge_batch* b, int32_t g, hge_batch_commits* out) {
+  if (!b || !out || g < 0 || g >= (int)b->gs.size()) return HGE_ERR_ARG;
+  if (!b->ran || !b->delivered) {
+    b->err = "hge_batch_commits_view: the last run did not deliver (hge_batch_set_delivery, then hge_batch_run)";
+    return HGE_ERR_ARG;
+  }
+  const GDesc& d = b->hd[g];
+  const bool rec = (b->delivered_what & 2) != 0;
+  out->ids = b->h_ids.h + d.eo;
+  out->rr = rec ? b->h_orr.h + d.eo : nullptr;
+  out->cts = rec ? b->h_octs.h + d.eo : nullptr;
+  out->counts = b->h_counts.h + d.co;
+  out->ordered = b->h_scal[(size_t)g * 8 + 4];
+  out->calls = d.K;
+  return HGE_OK;
+}
 
 int hge_batch_kernel_ms(hge_batch* b, float* ms, int32_t cap) {
   if (!b || (!ms && cap > 0)) return HGE_ERR_ARG;

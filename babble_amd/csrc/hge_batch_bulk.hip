@@ -768,9 +768,11 @@ __global__ __launch_bounds__(1024) void kb_order_prep(BT t) {
 // (rr - rmin) << 60 | (cts - cmin) << 32 | S >> 32 when the bucket's rounds span
 // under 16 and its timestamps under 2^28 ns (else the prefix is 0); equal prefixes
 // compare the full key from HBM (consensus_sorter.go:36-59, PRN = 0).
-// kb_sort<TPB, LO, CAP> takes the buckets of LO < n <= CAP keys, TPB threads per
+// kb_sort<TPB, LO, CAP, DLV> takes the buckets of LO < n <= CAP keys, TPB threads per
 // bucket (one wave while the batch has many buckets, four while it has few); the
-// largest class sorts buckets past CAP on their full keys in HBM.
+// largest class sorts buckets past CAP on their full keys in HBM.  DLV: the sorted
+// keys' round received and timestamp are stored beside the ids, in commit order
+// (BT::ord_rr / ord_cts, the delivery mode of hge_batch_set_delivery).
 __device__ __forceinline__ void bitonic_pair(int q, int size, int stride, int& a, int& b) {
   if (stride == size >> 1) {  // merge: mirrored pairs
     const int blk = q / stride, i = q - blk * stride;
@@ -789,7 +791,7 @@ __device__ __forceinline__ int64_t wave_max64(int64_t v) {
   for (int o = 32; o > 0; o >>= 1) v = max(v, (int64_t)__shfl_xor(v, o));
   return v;
 }
-template <int TPB, int LO, int CAP>
+template <int TPB, int LO, int CAP, bool DLV>
 __global__ __launch_bounds__(TPB) void kb_sort(BT t, int last) {
   __shared__ uint64_t lk[CAP];
   __shared__ uint16_t lx[CAP];
@@ -874,6 +876,11 @@ __global__ __launch_bounds__(TPB) void kb_sort(BT t, int last) {
         }
       sync(true);
       for (int k = tid; k < n; k += TPB) t.order[eo + base + k] = t.kid[so + lx[k]];
+      if (DLV)  // the commit records beside the ids
+        for (int k = tid; k < n; k += TPB) {
+          t.ord_rr[eo + base + k] = t.krr[so + lx[k]];
+          t.ord_cts[eo + base + k] = t.kct[so + lx[k]];
+        }
       sync(true);  // the LDS keys are the next bucket's
     } else {
       for (int size = 2; size <= P; size <<= 1) {
@@ -902,6 +909,11 @@ __global__ __launch_bounds__(TPB) void kb_sort(BT t, int last) {
         }
       }
       for (int k = tid; k < n; k += TPB) t.order[eo + base + k] = ld(t.kid + so + k);
+      if (DLV)
+        for (int k = tid; k < n; k += TPB) {
+          t.ord_rr[eo + base + k] = ld(t.krr + so + k);
+          t.ord_cts[eo + base + k] = ld(t.kct + so + k);
+        }
       __syncthreads();
     }
   }

@@ -94,12 +94,29 @@ EXPORTS = [
     # a batch of independent hashgraphs (config 5, hge_batch.hip)
     "hge_batch_create", "hge_batch_destroy", "hge_batch_last_error", "hge_batch_add", "hge_batch_stage",
     "hge_batch_run", "hge_batch_graphs", "hge_batch_info", "hge_batch_results", "hge_batch_kernel_ms",
-    "hge_batch_fallbacks",
+    "hge_batch_fallbacks", "hge_batch_set_delivery", "hge_batch_delivery", "hge_batch_commits_view",
     # the wire / hashing format (host only, hge_gob.cpp)
     "hge_gob_encode_wire_events", "hge_gob_decode_wire_events", "hge_gob_encode_event_body",
 ]
 
 _lib = None
+
+
+class BatchCommits(ctypes.Structure):
+    """hge_batch_commits (hge.h)."""
+    _fields_ = [("ids", ctypes.POINTER(ctypes.c_int32)), ("rr", ctypes.POINTER(ctypes.c_int32)),
+                ("cts", ctypes.POINTER(ctypes.c_int64)), ("counts", ctypes.POINTER(ctypes.c_int64)),
+                ("ordered", ctypes.c_int64), ("calls", ctypes.c_int64)]
+
+
+class _HostView:
+    """A read-only window on memory owned by `owner`, for np.asarray: the array's
+    base is this object, so the owner lives as long as any array over its memory."""
+
+    def __init__(self, owner, pointer, n, typestr):
+        self.owner = owner
+        self.__array_interface__ = dict(shape=(int(n),), typestr=typestr, version=3,
+                                        data=(ctypes.cast(pointer, ctypes.c_void_p).value, True))
 
 
 class HgeError(RuntimeError):
@@ -253,6 +270,11 @@ def lib():
     L.hge_batch_kernel_ms.argtypes = [vp, P(ctypes.c_float), i32]
     L.hge_batch_fallbacks.argtypes = [vp]
     L.hge_batch_fallbacks.restype = ctypes.c_int64
+    if hasattr(L, "hge_batch_set_delivery"):  # (a build of an older tree, HGE_LIB, lacks them)
+        L.hge_batch_set_delivery.argtypes = [vp, ctypes.c_uint32]
+        L.hge_batch_delivery.argtypes = [vp]
+        L.hge_batch_delivery.restype = i32
+        L.hge_batch_commits_view.argtypes = [vp, i32, P(BatchCommits)]
     _lib = L
     return L
 
@@ -1037,6 +1059,39 @@ class Batch:
         m = ctypes.c_int64()
         self._check(self.L.hge_batch_run(self.h, ctypes.byref(m)))
         return m.value
+
+    def deliver(self, order=True, received=False):
+        """Choose what the next stage()/run() delivers to host memory inside the run
+        (hge_batch_set_delivery): the consensus order and per-call batch sizes
+        (order), and with them each ordered event's round received and consensus
+        timestamp in commit order (received).  deliver(False) turns it off, the
+        default: a run then takes the path it takes without this mode.  received
+        without order is refused."""
+        self._check(self.L.hge_batch_set_delivery(self.h, (1 if order else 0) | (2 if received else 0)))
+
+    def delivered(self):
+        """How the last run delivered (hge_batch_delivery): 0 not at all, 1 the kernels
+        wrote the streams into mapped pinned memory, 2 copied after the run (the pinned
+        allocation failed, or HGB_TEST_NO_PIN=1)."""
+        return int(self.L.hge_batch_delivery(self.h))
+
+    def commits(self, g):
+        """Graph g's commit stream of the last run, which must have delivered:
+        dict(ids, rr, cts, counts) of read-only numpy arrays over the batch's own host
+        buffers, without a copy (rr and cts are None unless deliver(received=True)).
+        ids is the consensus order call by call, counts the calls' batch sizes, rr[k]
+        and cts[k] the round received and consensus timestamp of ids[k].
+
+        The arrays are views: their contents are defined until the next add(), stage(),
+        run(), deliver() or close() of this Batch, which may rewrite or free the memory
+        under them; copy what has to outlive that.  Each array keeps a reference to the
+        Batch, so dropping the Batch while holding a view does not free the buffers."""
+        c = BatchCommits()
+        self._check(self.L.hge_batch_commits_view(self.h, g, ctypes.byref(c)))
+        n, k = c.ordered, c.calls
+        view = lambda p, m, t: np.asarray(_HostView(self, p, m, t)) if p else None
+        return dict(ids=view(c.ids, n, "<i4"), rr=view(c.rr, n, "<i4"), cts=view(c.cts, n, "<i8"),
+                    counts=view(c.counts, k, "<i8"))
 
     def graphs(self):
         return self.L.hge_batch_graphs(self.h)

@@ -245,6 +245,34 @@ int hge_batch_kernel_ms(hge_batch* b, float* ms, int32_t cap);
 /* graphs the last run replayed call by call (kb_consensus) because the bulk fold
  * could not hold them (more than 256 rounds, or a receive-interval table overflow) */
 int64_t hge_batch_fallbacks(hge_batch* b);
+/* Delivery of the commit stream (what FindOrder hands its caller, hashgraph.go:723-760)
+ * to host memory inside the run.  Off by default: a run then takes exactly the path it
+ * takes without this mode and the orders stay on the device (hge_batch_results copies
+ * them).  With it on, the sort and consensus kernels store each graph's stream through
+ * a mapped pinned allocation, so it is in host memory when hge_batch_run returns, with
+ * no further copy.
+ * what: bit 0 = the consensus order and the per-call batch sizes;
+ *       bit 1 = also each ordered event's round received and consensus timestamp, in commit order.
+ * 0 = off (default).  Takes effect at the next stage/run.  Bit 1 without bit 0 is HGE_ERR_ARG. */
+int hge_batch_set_delivery(hge_batch* b, uint32_t what);
+/* after a run: 0 = not delivered, 1 = written by the kernels into mapped pinned memory,
+ * 2 = the pinned allocation failed (or the test hook HGB_TEST_NO_PIN=1): same buffers filled by
+ * one pooled copy per field after the run */
+int32_t hge_batch_delivery(hge_batch* b);
+typedef struct {
+  const int32_t* ids;     /* [ordered] graph-local event ids, the ConsensusSorter order call by call */
+  const int32_t* rr;      /* [ordered] round received of ids[k]          (NULL unless bit 1) */
+  const int64_t* cts;     /* [ordered] consensus timestamp of ids[k]     (NULL unless bit 1) */
+  const int64_t* counts;  /* [calls]   batch size of each call */
+  int64_t ordered, calls;
+} hge_batch_commits;
+/* Graph g's commit stream of the last run: views into the batch's own host buffers, valid until the next
+ * add / stage / run / set_delivery / destroy.  HGE_ERR_ARG if the last run did not deliver.
+ * The buffers are pooled like the device tables (one allocation per field for the whole
+ * batch, graph g at its event / call offset), sized at stage time, reused across runs and
+ * freed by hge_batch_destroy.  After a delivering run hge_batch_results takes order and
+ * counts from them as well. */
+int hge_batch_commits_view(hge_batch* b, int32_t g, hge_batch_commits* out);
 
 /* ---- one hashgraph split across GPUs (babble_amd/dist.py) ------ */
 /* Sharded replay.  Every rank stages the whole stream (hge_replay_prepare) and
