@@ -491,6 +491,7 @@ struct hge_engine {
     s_cn.free_();
     s_mb.free_();
     s_wpaths.free_();
+    s_spaths.free_();
     s_hist.free_();
     s_hstate.free_();
     s_hssc.free_();
@@ -1656,6 +1657,23 @@ struct hge_engine {
     walk_seq++;
     return s_wpaths.p + 2 * (walk_seq & 1);
   }
+  // The order stage's sort-path counters (hge_sort_paths): two slots of {packed, index,
+  // k_bucket_sort_big's next bucket, unused}, handed over like the walk's.  An order stage without a bucket past 512 keys launches
+  // no counting kernel and reports (0, 0).
+  DBuf<unsigned long long> s_spaths;
+  int sort_seq = 0;
+  bool sort_counted = false;
+  SortCtl sort_ctl() {
+    if (!s_spaths.p) {
+      s_spaths.need(8);
+      HIPCHK(hipMemset(s_spaths.p, 0, 8 * sizeof(unsigned long long)));
+    }
+    sort_seq++;
+    sort_counted = true;
+    const char* e = getenv("HGE_TEST_SORT_INDEX");  // tests: every bucket takes the index sort
+    return SortCtl{s_spaths.p + 4 * (sort_seq & 1), s_spaths.p + 4 * ((sort_seq + 1) & 1),
+                   e && atoi(e) != 0 ? 1 : 0};
+  }
   // tests (HGE_TEST_DIR_EXACT=1): every round of the walk takes the 16-bit select
   static int walk_force_exact() {
     const char* e = getenv("HGE_TEST_DIR_EXACT");
@@ -2387,6 +2405,7 @@ struct hge_engine {
     oc.n1 = (int)n_coords;
     oc.lcre_out = out_word(hge_plan::ResultsLayout::kLcrEvents);
     oc.front = front;
+    oc.sort = sort_ctl();
     return oc;
   }
 
@@ -2593,10 +2612,11 @@ struct hge_engine {
       ids_dst = pin_ord_dev;
       b.wrote_direct = true;
     }
+    sort_counted = false;
     if (ncalls <= 8) {
       // a few buckets (an online call): one launch, each bucket to the path its size takes
       KLAUNCH(k_bucket_sort_all, dim3(ncalls), dim3(1024), 0, st, (const int32_t*)s_bpos.p,
-              (const int32_t*)o_cc, (const int32_t*)blist, (const int32_t*)nblist, k1, k2, ids_dst);
+              (const int32_t*)o_cc, (const int32_t*)blist, (const int32_t*)nblist, k1, k2, ids_dst, sort_ctl());
     } else {
       // buckets of 513 .. 2 * BIG_SORT keys in LDS (k_bucket_sort_big), the rest here
       KLAUNCH(k_bucket_sort, dim3(std::min(ncalls, 2048)), dim3(256), 0, st,
@@ -2605,7 +2625,7 @@ struct hge_engine {
       if (ncand > 512)  // (no bucket past 512 keys otherwise)
         KLAUNCH(k_bucket_sort_big, dim3(std::min(ncalls, n_cu())), dim3(1024), 0, st,
                 (const int32_t*)s_bpos.p, (const int32_t*)o_cc, (const int32_t*)blist,
-                (const int32_t*)nblist, (const OKey*)k1, k2, ids_dst);
+                (const int32_t*)nblist, (const OKey*)k1, k2, ids_dst, sort_ctl());
     }
     // new undetermined list (in candidate order), scattered into the spare list
     // (same capacity) and swapped: no device copy
@@ -4063,6 +4083,19 @@ int hge_walk_select_paths(hge_engine* h, int64_t* narrow, int64_t* exact) {
   }
   if (narrow) *narrow = (int64_t)v[0];
   if (exact) *exact = (int64_t)v[1];
+  return HGE_OK;
+  GUARD_END(h)
+}
+
+int hge_sort_paths(hge_engine* h, int64_t* packed, int64_t* index) {
+  GUARD_BEGIN
+  unsigned long long v[2] = {0, 0};
+  if (h->s_spaths.p && h->sort_counted) {
+    h->d2h(v, h->s_spaths.p + 4 * (h->sort_seq & 1), 16);
+    h->sync();
+  }
+  if (packed) *packed = (int64_t)v[0];
+  if (index) *index = (int64_t)v[1];
   return HGE_OK;
   GUARD_END(h)
 }

@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hge_sortkey.h"
+
 #define INF32 0x7FFFFFFF
 
 namespace hge {
@@ -2903,31 +2905,298 @@ __device__ void big_bitonic(const OKey* K, int n, uint64_t* sb, uint32_t* sr, ui
   }
 }
 
+// The same sort over the keys themselves: each key packed into one
+// 64-bit word (hge_sortkey.h: rr and cts relative to the bucket's minima, then the top
+// 32 bits of S) with its 16-bit local index, E consecutive elements per thread
+// (E = 4 up to 4,096 slots, 8 at 8,192).  Strides below E are compare-exchanges in
+// registers, strides E .. 32 E lane exchanges inside the wave.  The strides across waves
+// go through LDS as a transposition: the thread of wave w, lane l trades places with the
+// thread of wave l & m, lane (l & ~m) | w (m = waves - 1), which turns every
+// cross-wave stride of a merge into a lane exchange; one transposition in, the strides,
+// one back -- 8 LDS passes at 4,096 slots where the index sort has 78 stages of dependent
+// gathers.  The LDS image is one 8-byte word per element and thread (E arrays of P / E)
+// and the indices of a thread as 8-byte groups, the thread's slot inside its wave
+// xor-ed with the wave number: stores and the transposed loads are conflict-free.
+// Equal words (rare: equal medians and equal leading bits of S) are ordered by the full
+// key from HBM, padding by index, as in big_bitonic: the same total order, so the same
+// ix[0, n).  Returns false, having sorted nothing, when the bucket is not packable.
+constexpr size_t BIG_LDS = (size_t)BIG_SORT * (8 + 4 + 4 + 2);  // big_bitonic's arrays: sb, sr, ss, ix
+// (the packed image, 10 bytes per slot, stays below ix at 16 bytes per slot)
+
+__device__ __forceinline__ bool pk_less(uint64_t wa, uint32_t ia, uint64_t wb, uint32_t ib, const OKey* K, int n) {
+  if (wa != wb) return wa < wb;
+  if (ia >= (uint32_t)n || ib >= (uint32_t)n) return ia < ib;  // padding (a real key comes first)
+  // equal words: okless over the full keys, a field at a time (the rare branch sits in
+  // every unrolled compare: it must not hold two whole keys in registers)
+  const uint64_t* x = (const uint64_t*)&K[ia];
+  const uint64_t* y = (const uint64_t*)&K[ib];
+#pragma unroll 1
+  for (int f = 0; f < 6; f++) {  // a, b, s0 .. s3
+    const uint64_t xf = x[f], yf = y[f];
+    if (xf != yf) return xf < yf;
+  }
+  return K[ia].id < K[ib].id;
+}
+static_assert(sizeof(OKey) == 56 && offsetof(OKey, id) == 48, "pk_less walks a .. s3 as six words");
+
+// v of lane ^ X without the LDS crossbar (a counter pass put the __shfl_xor form's
+// ds_bpermute at over half of the kernel's cycles): DPP quad permutes and row rotates
+// up to 8 lanes, gfx950's row and half-wave swaps for 16 and 32.  Whole waves only.
+template <int CTRL>
+__device__ __forceinline__ uint32_t pk_dpp(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
+}
+template <int X>
+__device__ __forceinline__ uint32_t pk_xor(uint32_t v, int lane) {
+  if constexpr (X == 1) {
+    return pk_dpp<0xB1>(v);  // quad_perm [1, 0, 3, 2]
+  } else if constexpr (X == 2) {
+    return pk_dpp<0x4E>(v);  // quad_perm [2, 3, 0, 1]
+  } else if constexpr (X == 4) {
+    return pk_dpp<0x1B>(pk_dpp<0x141>(v));  // row_half_mirror (^7), then quad_perm [3, 2, 1, 0] (^3)
+  } else if constexpr (X == 8) {
+    return pk_dpp<0x128>(v);  // row_ror 8
+  } else if constexpr (X == 16) {
+    // odd rows of the first copy swapped with even rows of the second
+    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    return (lane & 16) ? r[0] : r[1];
+  } else {
+    // the upper half of the first copy swapped with the lower half of the second
+    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return (lane & 32) ? r[0] : r[1];
+  }
+}
+
+// one stride inside the wave: the partner is lane ^ X; pos = the thread's first slot
+template <int E, int X>
+__device__ __forceinline__ void pk_lane_stage_x(uint64_t (&w)[E], uint32_t (&id)[E], int lane, uint32_t pos, int size,
+                                                const OKey* K, int n) {
+  const bool want_min = ((lane & X) == 0) == ((pos & (uint32_t)size) == 0);
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const uint64_t ow = (uint64_t)pk_xor<X>((uint32_t)w[e], lane) | ((uint64_t)pk_xor<X>((uint32_t)(w[e] >> 32), lane) << 32);
+    const uint32_t oi = pk_xor<X>(id[e], lane);
+    const bool take = pk_less(ow, oi, w[e], id[e], K, n) == want_min;
+    w[e] = take ? ow : w[e];
+    id[e] = take ? oi : id[e];
+  }
+}
+template <int E>
+__device__ __forceinline__ void pk_lane_stage(uint64_t (&w)[E], uint32_t (&id)[E], int x, int lane, uint32_t pos,
+                                              int size, const OKey* K, int n) {
+  switch (x) {  // (wave-uniform)
+    case 1: pk_lane_stage_x<E, 1>(w, id, lane, pos, size, K, n); break;
+    case 2: pk_lane_stage_x<E, 2>(w, id, lane, pos, size, K, n); break;
+    case 4: pk_lane_stage_x<E, 4>(w, id, lane, pos, size, K, n); break;
+    case 8: pk_lane_stage_x<E, 8>(w, id, lane, pos, size, K, n); break;
+    case 16: pk_lane_stage_x<E, 16>(w, id, lane, pos, size, K, n); break;
+    default: pk_lane_stage_x<E, 32>(w, id, lane, pos, size, K, n); break;
+  }
+}
+
+template <int E>
+__device__ __forceinline__ bool packed_bitonic(const OKey* K, int n, int P, unsigned char* pool, uint16_t* ix) {
+  // (opaque per call: the thread's slots, addresses and masks of every inlined sort are
+  // otherwise hoisted to the kernel's entry and held across all of them, ~60 registers)
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wv = tid >> 6;
+  const int NT = P / E;  // threads that hold elements: whole waves, 4 .. 16 of them
+  const bool act = tid < NT;
+  uint32_t rmin = 0xFFFFFFFFu, rmax = 0;
+  uint64_t bmin = ~0ull, bmax = 0;
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int i = tid * E + e;
+    if (act && i < n) {
+      const uint32_t r = (uint32_t)K[i].a;  // rr (the call is the bucket's)
+      const uint64_t b = K[i].b;
+      rmin = min(rmin, r);
+      rmax = max(rmax, r);
+      bmin = b < bmin ? b : bmin;
+      bmax = b > bmax ? b : bmax;
+    }
+  }
+  // the bucket's ranges: waves, then the block through LDS
+  for (int o = 32; o > 0; o >>= 1) {
+    rmin = min(rmin, (uint32_t)__shfl_xor(rmin, o));
+    rmax = max(rmax, (uint32_t)__shfl_xor(rmax, o));
+    const uint64_t a = __shfl_xor(bmin, o), b = __shfl_xor(bmax, o);
+    bmin = a < bmin ? a : bmin;
+    bmax = b > bmax ? b : bmax;
+  }
+  uint64_t* red = (uint64_t*)pool;
+  if (lane == 0) {
+    red[4 * wv] = rmin;
+    red[4 * wv + 1] = rmax;
+    red[4 * wv + 2] = bmin;
+    red[4 * wv + 3] = bmax;
+  }
+  __syncthreads();
+  for (int v = 0; v < (int)(blockDim.x >> 6); v++) {
+    rmin = min(rmin, (uint32_t)red[4 * v]);
+    rmax = max(rmax, (uint32_t)red[4 * v + 1]);
+    bmin = red[4 * v + 2] < bmin ? red[4 * v + 2] : bmin;
+    bmax = red[4 * v + 3] > bmax ? red[4 * v + 3] : bmax;
+  }
+  __syncthreads();  // (the first transposition writes over red)
+  const hge_sortkey::SkPlan plan = hge_sortkey::sk_plan(rmin, rmax, bmin, bmax);
+  if (!plan.packable) return false;  // block-uniform
+  uint64_t w[E];
+  uint32_t id[E];
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int i = tid * E + e;
+    // (the keys a second time, from the cache: kept in registers across the reduction they
+    // cost 4 E registers through the whole sort's allocation)
+    w[e] = act && i < n ? hge_sortkey::sk_word(plan, (uint32_t)K[i].a, K[i].b, K[i].s0) : hge_sortkey::kSkPad;
+    id[e] = (uint32_t)i;
+  }
+  const int m = (NT >> 6) - 1;
+  const int ptid = ((lane & m) << 6) | (lane & ~m) | (wv & m);  // the thread this one trades places with
+  const uint32_t posA = (uint32_t)tid * E, posB = (uint32_t)ptid * E;
+  // (rows of 1,024 whatever NT is: the rows' offsets are immediates of the LDS instructions)
+  constexpr int LR = 1024;
+  uint64_t* const lw = (uint64_t*)pool;  // [E][LR] words
+  uint64_t* const li = lw + E * LR;      // [E / 4][LR] four indices each
+  auto slot = [](int t) { return (t & ~63) | ((t ^ (t >> 6)) & 63); };
+  auto transpose = [&]() {
+    if (act) {
+      const int s = slot(tid);
+#pragma unroll
+      for (int e = 0; e < E; e++) lw[e * LR + s] = w[e];
+#pragma unroll
+      for (int g = 0; g < E / 4; g++)
+        li[g * LR + s] = (uint64_t)id[4 * g] | ((uint64_t)id[4 * g + 1] << 16) | ((uint64_t)id[4 * g + 2] << 32) |
+                         ((uint64_t)id[4 * g + 3] << 48);
+    }
+    __syncthreads();
+    if (act) {
+      const int s = slot(ptid);
+#pragma unroll
+      for (int e = 0; e < E; e++) w[e] = lw[e * LR + s];
+#pragma unroll
+      for (int g = 0; g < E / 4; g++) {
+        const uint64_t v = li[g * LR + s];
+        id[4 * g] = (uint32_t)v & 0xFFFFu;
+        id[4 * g + 1] = (uint32_t)(v >> 16) & 0xFFFFu;
+        id[4 * g + 2] = (uint32_t)(v >> 32) & 0xFFFFu;
+        id[4 * g + 3] = (uint32_t)(v >> 48);
+      }
+    }
+    __syncthreads();
+  };
+  for (int size = 2; size <= P; size <<= 1) {
+    int j = size >> 1;
+    if (j >= 64 * E) {  // the strides across waves, as lane exchanges of the transposed layout
+      transpose();
+      if (act)
+        for (; j >= 64 * E; j >>= 1) pk_lane_stage<E>(w, id, j / (64 * E), lane, posB, size, K, n);
+      transpose();
+      j = 32 * E;
+    }
+    if (act) {
+      for (; j >= E; j >>= 1) pk_lane_stage<E>(w, id, j / E, lane, posA, size, K, n);
+#pragma unroll
+      for (int s = E / 2; s >= 1; s >>= 1) {
+        if (s >= size) continue;
+#pragma unroll
+        for (int lo = 0; lo < E; lo++) {
+          if (lo & s) continue;
+          const int hi = lo | s;
+          const bool up = ((posA + lo) & (uint32_t)size) == 0;
+          if (pk_less(w[hi], id[hi], w[lo], id[lo], K, n) == up) {
+            const uint64_t tw = w[lo];
+            w[lo] = w[hi];
+            w[hi] = tw;
+            const uint32_t ti = id[lo];
+            id[lo] = id[hi];
+            id[hi] = ti;
+          }
+        }
+      }
+    }
+  }
+  if (act) {
+#pragma unroll
+    for (int g = 0; g < E / 4; g++)
+      ((uint64_t*)ix)[tid * (E / 4) + g] = (uint64_t)id[4 * g] | ((uint64_t)id[4 * g + 1] << 16) |
+                                           ((uint64_t)id[4 * g + 2] << 32) | ((uint64_t)id[4 * g + 3] << 48);
+  }
+  __syncthreads();
+  return true;
+}
+
+// The order stage's sort-path counters (hge_sort_paths): two slots of {packed, index,
+// next bucket of k_bucket_sort_big, unused}; the stage adds to cur and clears next for
+// the stage after it on the stream (as the walk's select-path counters).  force_index
+// (HGE_TEST_SORT_INDEX=1): every bucket takes big_bitonic.
+struct SortCtl {
+  unsigned long long* cur;
+  unsigned long long* next;
+  int force_index;
+};
+__device__ __forceinline__ void sort_ctl_begin(const SortCtl& c) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && c.next) c.next[0] = c.next[1] = c.next[2] = 0;
+}
+
+// K[0, n) (n <= BIG_SORT) sorted into ix[0, n): packed where the bucket packs, else the
+// index sort; pool = big_bitonic's arrays (BIG_LDS bytes).  Returns the path (block-uniform).
+__device__ __forceinline__ bool big_sort_keys(const OKey* K, int n, unsigned char* pool, bool force_index) {
+  uint16_t* ix = (uint16_t*)(pool + (size_t)BIG_SORT * 16);
+  if (!force_index) {
+    int P = 1024;
+    while (P < n) P <<= 1;
+    if (P <= 4096 ? packed_bitonic<4>(K, n, P, pool, ix) : packed_bitonic<8>(K, n, P, pool, ix)) return true;
+  }
+  big_bitonic(K, n, (uint64_t*)pool, (uint32_t*)(pool + (size_t)BIG_SORT * 8),
+              (uint32_t*)(pool + (size_t)BIG_SORT * 12), ix);
+  return false;
+}
+
 // Buckets of BIG_SORT + 1 .. 2 * BIG_SORT keys (a call that receives more than one
 // round's worth: 33 calls of 8-16k keys at 256/10M) are two halves sorted in LDS
-// the same way, then one merge-path pass over their index lists (scratch: the
+// the same way (each half packed on its own ranges; one that does not pack takes the
+// index sort alone), then one merge-path pass over their index lists (scratch: the
 // bucket's slice of tmp), each thread placing nb / 1024 outputs from its co-rank.
-// one bucket of 513 .. 2 * BIG_SORT keys (block-uniform)
-__device__ void bucket_sort_big_one(int b, int nb, const int32_t* bend, const OKey* keys, OKey* tmp,
-                                    int32_t* ids_out, uint64_t* sb, uint32_t* sr, uint32_t* ss, uint16_t* ix) {
-  const int tid = threadIdx.x, T = blockDim.x;
+// one bucket of 513 .. 2 * BIG_SORT keys (block-uniform); counted as packed when every
+// sort of it was
+__device__ __forceinline__ void bucket_sort_big_one(int b, int nb, const int32_t* bend, const OKey* keys, OKey* tmp,
+                                    int32_t* ids_out, unsigned char* pool, const SortCtl& ctl) {
+  const int T = blockDim.x;
+  const uint16_t* ix = (const uint16_t*)(pool + (size_t)BIG_SORT * 16);
+  const bool fi = ctl.force_index != 0;
+  // (the thread index taken anew after each sort: what is derived from it for the writes
+  // below would otherwise be computed ahead of the sort and spilled across it)
+  auto thread = []() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+  };
   {
-    const OKey* K = keys + (bend[b] - nb);
-    int32_t* out = ids_out + (bend[b] - nb);
-    if (nb <= BIG_SORT) {
-      big_bitonic(K, nb, sb, sr, ss, ix);
-      for (int i = tid; i < nb; i += T) out[i] = (int32_t)K[ix[i]].id;
+    // (block-uniform values, told so: as scalars they cost no vector registers across the sort)
+    nb = __builtin_amdgcn_readfirstlane(nb);
+    const int start = __builtin_amdgcn_readfirstlane(bend[b] - nb);
+    const OKey* K = keys + start;
+    int32_t* out = ids_out + start;
+    int32_t* S = (int32_t*)(tmp + start);  // 4 of the 48 scratch bytes per key
+    const bool whole = nb <= BIG_SORT;
+    const int na = whole ? nb : (nb + 1) >> 1, nbb = nb - na;
+    bool pk = true;
+    for (int h = 0; h < (whole ? 1 : 2); h++) {  // (one call site: the sorts are inlined once)
+      const int off = h ? na : 0, len = h ? nbb : na;
+      pk = big_sort_keys(K + off, len, pool, fi) && pk;
+      const int tid = thread();
+      if (whole) {
+        for (int i = tid; i < len; i += T) out[i] = (int32_t)K[ix[i]].id;
+      } else {
+        for (int i = tid; i < len; i += T) S[off + i] = off + ix[i];
+      }
       __syncthreads();
-      return;
     }
-    int32_t* S = (int32_t*)(tmp + (bend[b] - nb));  // 4 of the 48 scratch bytes per key
-    const int na = (nb + 1) >> 1, nbb = nb - na;
-    big_bitonic(K, na, sb, sr, ss, ix);
-    for (int i = tid; i < na; i += T) S[i] = ix[i];
-    __syncthreads();
-    big_bitonic(K + na, nbb, sb, sr, ss, ix);
-    for (int i = tid; i < nbb; i += T) S[na + i] = na + ix[i];
-    __syncthreads();
+    const int tid = thread();
+    if (tid == 0 && ctl.cur) atomicAdd(&ctl.cur[pk ? 0 : 1], 1ull);
+    if (whole) return;
     const int32_t* A = S;
     const int32_t* B = S + na;
     const int k0 = (int)((int64_t)nb * tid / T), k1 = (int)((int64_t)nb * (tid + 1) / T);
@@ -2948,15 +3217,24 @@ __device__ void bucket_sort_big_one(int b, int nb, const int32_t* bend, const OK
 
 __global__ void __launch_bounds__(1024) k_bucket_sort_big(const int32_t* bend, const int32_t* bcnt,
                                                           const int32_t* list, const int32_t* nlist,
-                                                          const OKey* keys, OKey* tmp, int32_t* ids_out) {
-  __shared__ uint64_t sb[BIG_SORT];
-  __shared__ uint32_t sr[BIG_SORT], ss[BIG_SORT];
-  __shared__ uint16_t ix[BIG_SORT];
-  for (int li = blockIdx.x; li < *nlist; li += gridDim.x) {
+                                                          const OKey* keys, OKey* tmp, int32_t* ids_out, SortCtl ctl) {
+  __shared__ __attribute__((aligned(16))) unsigned char pool[BIG_LDS];
+  __shared__ int s_li;
+  sort_ctl_begin(ctl);
+  // The buckets dealt out by a counter, not by stride: a 4-8k-key bucket costs two of
+  // the usual 2-4k ones and an 8-16k one five, and a block that met one by stride
+  // finished a third after the average.
+  const int nl = *nlist;
+  for (;;) {
+    if (threadIdx.x == 0) s_li = (int)atomicAdd(&ctl.cur[2], 1ull);
+    __syncthreads();
+    const int li = s_li;
+    __syncthreads();  // (read by all before the next one is taken)
+    if (li >= nl) break;
     const int b = list[li];
     const int nb = bcnt[b];
     if (nb <= 512 || nb > 2 * BIG_SORT) continue;  // block-uniform
-    bucket_sort_big_one(b, nb, bend, keys, tmp, ids_out, sb, sr, ss, ix);
+    bucket_sort_big_one(b, nb, bend, keys, tmp, ids_out, pool, ctl);
   }
 }
 
@@ -2965,19 +3243,15 @@ __global__ void __launch_bounds__(1024) k_bucket_sort_big(const int32_t* bend, c
 // (one launch in place of k_bucket_sort + k_bucket_sort_big)
 __global__ void __launch_bounds__(1024) k_bucket_sort_all(const int32_t* bend, const int32_t* bcnt,
                                                           const int32_t* list, const int32_t* nlist,
-                                                          OKey* keys, OKey* tmp, int32_t* ids_out) {
-  constexpr size_t BIG_LDS = (size_t)BIG_SORT * (8 + 4 + 4 + 2);
+                                                          OKey* keys, OKey* tmp, int32_t* ids_out, SortCtl ctl) {
   constexpr size_t POOL = BIG_LDS > sizeof(SortChunk<SORT_CH>) ? BIG_LDS : sizeof(SortChunk<SORT_CH>);
   __shared__ __attribute__((aligned(16))) unsigned char pool[POOL];
-  uint64_t* sb = (uint64_t*)pool;
-  uint32_t* sr = (uint32_t*)(pool + (size_t)BIG_SORT * 8);
-  uint32_t* ss = (uint32_t*)(pool + (size_t)BIG_SORT * 12);
-  uint16_t* ix = (uint16_t*)(pool + (size_t)BIG_SORT * 16);
   SortChunk<SORT_CH>& sc = *(SortChunk<SORT_CH>*)pool;
+  sort_ctl_begin(ctl);
   for (int li = blockIdx.x; li < *nlist; li += gridDim.x) {
     const int b = list[li];
     const int nb = bcnt[b];
-    if (nb > 512 && nb <= 2 * BIG_SORT) bucket_sort_big_one(b, nb, bend, keys, tmp, ids_out, sb, sr, ss, ix);
+    if (nb > 512 && nb <= 2 * BIG_SORT) bucket_sort_big_one(b, nb, bend, keys, tmp, ids_out, pool, ctl);
     else bucket_sort_one(b, bend, bcnt, keys, tmp, ids_out, false, sc);
     __syncthreads();
   }
@@ -3169,8 +3443,9 @@ struct OrderCall {
   int lcr_old, n_lo, n1;
   int32_t* lcre_out;
   int front;  // 1: the segments and round received here too (N <= 16); 0: from the stage kernels
+  SortCtl sort;  // the sort-path counters and the test hook
 };
-constexpr size_t OC_BIG_LDS = (size_t)BIG_SORT * (8 + 4 + 4 + 2);
+constexpr size_t OC_BIG_LDS = BIG_LDS;
 constexpr size_t OC_POOL = OC_BIG_LDS > sizeof(SortChunk<SORT_CH>) ? OC_BIG_LDS : sizeof(SortChunk<SORT_CH>);
 static_assert(OC_POOL >= sizeof(int) * (SCAN_LDS + SCAN_LDS / 16), "the scan borrows the sort pool");
 template <int G>
@@ -3220,16 +3495,13 @@ __device__ __forceinline__ void order_call_body(const Tables& t, const OrderCall
   __syncthreads();
   // the sort (k_bucket_sort_all's path for the bucket's size)
   {
-    uint64_t* sb = (uint64_t*)pool;
-    uint32_t* sr = (uint32_t*)(pool + (size_t)BIG_SORT * 8);
-    uint32_t* ss = (uint32_t*)(pool + (size_t)BIG_SORT * 12);
-    uint16_t* ix = (uint16_t*)(pool + (size_t)BIG_SORT * 16);
     SortChunk<SORT_CH>& sc = *(SortChunk<SORT_CH>*)pool;
+    sort_ctl_begin(o.sort);
     const int nl = *o.nblist;
     for (int li = 0; li < nl; li++) {
       const int b = o.blist[li];
       const int nb = o.cnt[b];
-      if (nb > 512 && nb <= 2 * BIG_SORT) bucket_sort_big_one(b, nb, o.bpos, o.k1, o.k2, o.ids, sb, sr, ss, ix);
+      if (nb > 512 && nb <= 2 * BIG_SORT) bucket_sort_big_one(b, nb, o.bpos, o.k1, o.k2, o.ids, pool, o.sort);
       else bucket_sort_one(b, o.bpos, o.cnt, o.k1, o.k2, o.ids, false, sc);
       __syncthreads();
     }

@@ -73,7 +73,7 @@ EXPORTS = [
     "hge_fame", "hge_round_events", "hge_round_received", "hge_consensus_timestamp",
     "hge_consensus_timestamp_sources",
     "hge_ancestor", "hge_self_ancestor", "hge_see", "hge_strongly_see",
-    "hge_oldest_self_ancestor_to_see", "hge_coordinates", "hge_coordinate_sweeps", "hge_walk_select_paths", "hge_host_syncs", "hge_frontier_fallbacks",
+    "hge_oldest_self_ancestor_to_see", "hge_coordinates", "hge_coordinate_sweeps", "hge_walk_select_paths", "hge_sort_paths", "hge_host_syncs", "hge_frontier_fallbacks",
     "hge_stage_times",
     "hge_set_profiling", "hge_reset_kernel_stats", "hge_kernel_stats",
     "hge_consensus_log", "hge_event_rounds", "hge_event_received", "hge_set_cache_size",
@@ -188,6 +188,8 @@ def lib():
     L.hge_coordinate_sweeps.argtypes = [vp]
     if hasattr(L, "hge_walk_select_paths"):  # (a diagnostic build of an older tree, HGE_LIB, lacks it)
         L.hge_walk_select_paths.argtypes = [vp, P(i64), P(i64)]
+    if hasattr(L, "hge_sort_paths"):
+        L.hge_sort_paths.argtypes = [vp, P(i64), P(i64)]
     if hasattr(L, "hge_gob_encode_wire_events"):
         L.hge_gob_encode_wire_events.argtypes = [vp, i64, P(ctypes.c_uint8), P(i64), i32, P(ctypes.c_uint8), i64,
                                                  P(i64)]
@@ -788,6 +790,13 @@ class Engine:
         nar, ex = ctypes.c_int64(), ctypes.c_int64()
         self._check(self.L.hge_walk_select_paths(self.h, ctypes.byref(nar), ctypes.byref(ex)))
         return nar.value, ex.value
+
+    def sort_paths(self):
+        """(packed, index): call buckets of 513 .. 16,384 keys of the last order stage sorted
+        on packed keys in registers, and by the LDS index sort (hge_sort_paths)."""
+        pk, ix = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self.L.hge_sort_paths(self.h, ctypes.byref(pk), ctypes.byref(ix)))
+        return pk.value, ix.value
 
     def host_syncs(self):
         """Host round trips so far (waits on the engine stream)."""

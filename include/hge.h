@@ -531,6 +531,15 @@ int32_t hge_coordinate_sweeps(hge_engine* h);
  * by the 16-bit select (a round whose values leave the narrow range, or
  * HGE_TEST_DIR_EXACT=1).  Both 0 when no such walk has run. */
 int hge_walk_select_paths(hge_engine* h, int64_t* narrow, int64_t* exact);
+/* Call buckets of 513 .. 16,384 keys of the last order stage (FindOrder's sort) by
+ * path: sorted on packed 64-bit keys in registers (hge_sortkey.h), and by the LDS
+ * index sort (a bucket whose roundReceived and timestamp ranges do not fit 32 bits
+ * together, or every bucket with HGE_TEST_SORT_INDEX=1 in the environment, a test
+ * hook).  A bucket past 8,192 keys is sorted as two halves and counts as packed when
+ * both were.  Smaller and larger buckets take neither path and are not counted; both
+ * 0 when the last order stage had no such bucket.  Reads two device counters: one
+ * round trip per query, none in the order stage itself. */
+int hge_sort_paths(hge_engine* h, int64_t* packed, int64_t* index);
 /* Host round trips so far: the number of times the host has waited on the
  * engine's stream (each readback of a control value or result is one). */
 int64_t hge_host_syncs(hge_engine* h);
