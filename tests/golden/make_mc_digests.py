@@ -34,10 +34,16 @@ def graph_stream(g, p=PARAMS):
     return dag, schedule(len(dag["creator"]), p["k"])
 
 
-def oracle_state(dag, calls):
+def oracle_state(dag, calls, scale=False, stats=None):
+    """The oracle's full state of one replay.  scale: the oracle's scale mode (the same
+    results; the plain mode takes tens of seconds at 48k events).  stats (a dict): filled
+    with the oracle's DecideFame statistics."""
     from make_golden import describe
     from oracle.oracle import replay
-    o, status, order, counts = replay(dag, calls)
+    o, status, order, counts = replay(dag, calls, scale=scale)
+    assert o.is_scale() == bool(scale)
+    if stats is not None:
+        stats.update(o.stats())
     d = describe(o, dag, status, order, counts, calls)
     return {k: d[k] for k in ("status", "order", "counts", "rounds", "witness", "fame", "rr", "cts",
                               "undetermined", "scalars")}

@@ -27,6 +27,9 @@ CASES = [
     (7, 1200, 7, 14, 2, 0.1, 0.5, 0, 2),     # forks and cascades
     (16, 1200, 50, 21, 0, 0.0, 0.0, 6, 3),   # other-parents behind their chain's head
     (32, 1500, 32, 4, 10, 0.05, 0.5, 0, 3),  # config 5's shape
+    (8, 2400, 2400, 5, 0, 0.0, 0.0, 3, 3),   # one call: coin-bit votes taken (hashgraph.go:647) at N = 8
+    (5, 1500, 1500, 12, 0, 0.0, 0.0, 3, 3),  # and at N = 5
+    (32, 11000, 11000, 22, 0, 0.0, 0.0, 0, 3),  # one call: coin rounds at config 5's width
 ]
 
 
@@ -37,7 +40,12 @@ def test_bulk_model_matches_oracle(case):
     n, E, k, seed, fk, fp, cp, lag, ns = case
     dag = random_gossip(n, E, seed=seed, forkers=fk, fork_p=fp, cascade_p=cp, op_lag=lag)
     calls = schedule(len(dag["creator"]), k)
-    want = oracle_state(dag, calls)
+    stats = {}
+    want = oracle_state(dag, calls, stats=stats)
+    if lag == 3:  # the model's coin-bit vote is really taken
+        assert stats["coin_votes"] > 0
+    if (n, k) == (32, 11000):
+        assert stats["coin_evals"] > 0
     got = bulk_replay(dag, calls, want["status"], want["rounds"], want["witness"], NS=ns)
     for f in ("order", "counts", "fame", "undetermined", "scalars", "rr"):
         np.testing.assert_array_equal(np.asarray(got[f]), np.asarray(want[f]), err_msg=f)

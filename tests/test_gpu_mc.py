@@ -70,6 +70,7 @@ def test_monte_carlo_config5_batch_all_digests():
         for d, calls in streams:
             b.add(d, calls)
         tot = b.run()
+        assert b.fallbacks() == 0  # every graph in bulk: what the digests check is hge_batch_bulk.hip
         got = [b.state(g) for g in range(graphs)]
         bad = [g for g in range(graphs) if digest(got[g]) != ref["digests"][g]]
         assert not bad, f"graphs differing from the oracle digests: {bad[:16]}"

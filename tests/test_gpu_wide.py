@@ -273,16 +273,21 @@ def test_handoff_stall_mid_walk(n, events, k, epoch, monkeypatch):
         eng.close()
 
 
-@pytest.mark.parametrize("n,events", [(16, 3000), (32, 11000)])
-def test_coin_rounds_wide_one_shot(n, events):
+@pytest.mark.parametrize("n,events,seed", [(16, 3000, 77), (32, 11000, 78), (32, 11000, 22)],
+                         ids=["16-3000", "32-11000", "32-11000-seed22"])
+def test_coin_rounds_wide_one_shot(n, events, seed):
     """One RunConsensus over a whole stream long enough that DecideFame's j loop
     reaches diff = N (hashgraph.go:645-649, the coin branch) at N = 16 and N = 32:
     the engine equals the live oracle field by field, and the oracle's statistics
-    show the coin branch taken."""
+    show the coin branch taken.  With seed 78 the re-decisions leave the oracle's order
+    empty (fame and rounds are what is compared); with seed 22 it orders 10,236 events,
+    so everything downstream of the coin rounds is compared too."""
     from babble_amd.engine import Engine
     eng = Engine(n, events + 64)
     try:
-        o, _ = run_case(eng, random_gossip(n, events, seed=78 if n == 32 else 77), events)
+        o, order = run_case(eng, random_gossip(n, events, seed=seed), events)
         assert o.stats()["coin_evals"] > 0
+        if seed == 22:
+            assert 2 * len(order) > events
     finally:
         eng.close()
