@@ -48,10 +48,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/hge.h"
+#include "hge_hip.h"
 
 namespace hgb {
 
@@ -1462,33 +1465,8 @@ using namespace hgb;
 
 namespace {
 
-struct BatchError {
-  int code;
-  std::string msg;
-};
-
-#define BCHK(x)                                                                                \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess) throw BatchError{HGE_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-template <typename T>
-struct Buf {
-  T* p = nullptr;
-  size_t n = 0;
-  void need(size_t m) {
-    if (m <= n && p) return;
-    free_();
-    BCHK(hipMalloc(&p, std::max<size_t>(m, 1) * sizeof(T)));
-    n = m;
-  }
-  void free_() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
+using hge::DBuf;
+using hge::Error;
 
 // A host array of the commit stream: mapped pinned memory the kernels store to
 // (dev: its device-side address), or pageable memory that a copy fills after the run
@@ -1501,42 +1479,45 @@ struct HostField {
   bool pinned = false;
   void need(size_t n, bool try_pin) {
     if (h && n <= cap) return;
-    free_();
-    n = std::max<size_t>(n, 1);
-    if (try_pin) {
-      void *p = nullptr, *dp = nullptr;
-      if (hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) == hipSuccess) {
-        if (hipHostGetDevicePointer(&dp, p, 0) == hipSuccess && dp) {
-          h = (T*)p;
-          dev = (T*)dp;
-          pinned = true;
-        } else {
-          (void)hipHostFree(p);
-        }
-      }
-      if (!h) (void)hipGetLastError();  // not an error of the run: the copy path takes over
-    }
-    if (!h) {
-      h = (T*)malloc(n * sizeof(T));
-      if (!h) throw BatchError{HGE_ERR_INTERNAL, "commit stream: host allocation failed"};
-    }
-    cap = n;
-  }
-  void free_() {
-    if (h && pinned) (void)hipHostFree(h);
-    else free(h);
+    pin_ = hge::PBuf<T>();
+    page_.reset();
     h = dev = nullptr;
     cap = 0;
     pinned = false;
+    n = std::max<size_t>(n, 1);
+    if (try_pin) {
+      try {
+        pin_.need(n);
+        dev = hge::PinnedMem::device_ptr(pin_.p);
+      } catch (const Error&) {
+      }
+      if (dev) {
+        h = pin_.p;
+        pinned = true;
+      } else {
+        pin_ = hge::PBuf<T>();
+        (void)hipGetLastError();  // not an error of the run: the copy path takes over
+      }
+    }
+    if (!h) {
+      page_.reset(new (std::nothrow) T[n]);
+      if (!page_) throw Error{HGE_ERR_INTERNAL, "commit stream: host allocation failed"};
+      h = page_.get();
+    }
+    cap = n;
   }
+
+ private:
+  hge::PBuf<T> pin_;
+  std::unique_ptr<T[]> page_;
 };
 
 }  // namespace
 
 struct hge_batch {
   int N = 0, SM = 1, device = 0, ncu = 256;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[9] = {};
+  hge::Stream st;  // declared before every buffer and event: destroyed after them
+  hge::Event ev[9];
   std::string err;
   struct Graph {
     std::vector<int32_t> cr, ix, sp, op, oc, ntx;
@@ -1556,26 +1537,26 @@ struct hge_batch {
   static constexpr int NK = 8;  // coords, fd, fdrows, front, fame (prep + pairs), fold (+ theta), receive, order
   float kms[NK] = {};
   // device tables
-  Buf<GDesc> d_gd;
-  Buf<int32_t> d_cr, d_ix, d_sp, d_op, d_oc, d_ntx, d_clen, d_chain, d_LA, d_FDT, d_FD, d_round, d_rr, d_W, d_WIX,
+  DBuf<GDesc> d_gd;
+  DBuf<int32_t> d_cr, d_ix, d_sp, d_op, d_oc, d_ntx, d_clen, d_chain, d_LA, d_FDT, d_FD, d_round, d_rr, d_W, d_WIX,
       d_WFD;
-  Buf<int32_t> d_rcnt, d_ver, d_thv, d_th, d_U, d_Ur, d_Ucp, d_order, d_krr, d_kid;
-  Buf<int64_t> d_ts, d_tsch, d_calls, d_cts, d_counts, d_scal, d_kct;
-  Buf<uint64_t> d_Sch;
-  Buf<int32_t> d_ntxch;
-  Buf<uint64_t> d_S, d_ssb, d_seeb, d_ks0;
-  Buf<uint8_t> d_coin, d_wit, d_WCOIN;
-  Buf<int8_t> d_fame;
-  Buf<uint64_t> d_dbg;
+  DBuf<int32_t> d_rcnt, d_ver, d_thv, d_th, d_U, d_Ur, d_Ucp, d_order, d_krr, d_kid;
+  DBuf<int64_t> d_ts, d_tsch, d_calls, d_cts, d_counts, d_scal, d_kct;
+  DBuf<uint64_t> d_Sch;
+  DBuf<int32_t> d_ntxch;
+  DBuf<uint64_t> d_S, d_ssb, d_seeb, d_ks0;
+  DBuf<uint8_t> d_coin, d_wit, d_WCOIN;
+  DBuf<int8_t> d_fame;
+  DBuf<uint64_t> d_dbg;
   bool dbg_on = getenv("HGB_STAMPS") != nullptr;
   // the bulk call schedule; HGB_SERIAL=1 (test hook): every graph through kb_consensus
   bool serial = getenv("HGB_SERIAL") != nullptr;
-  Buf<int32_t> d_roundch, d_rrch, d_rslot, d_glist, d_cg, d_Rc, d_rfirst, d_rrank, d_xcall, d_gx, d_nivl, d_fsuf, d_thp, d_thR, d_rcall, d_bcnt, d_boff, d_wlc;
-  Buf<uint64_t> d_arr, d_Dp, d_ivF, d_thF;
-  Buf<int4> d_ivh;
-  Buf<int4> d_wl;
-  Buf<int2> d_cinf;
-  Buf<int64_t> d_gctx, d_ctsch;
+  DBuf<int32_t> d_roundch, d_rrch, d_rslot, d_glist, d_cg, d_Rc, d_rfirst, d_rrank, d_xcall, d_gx, d_nivl, d_fsuf, d_thp, d_thR, d_rcall, d_bcnt, d_boff, d_wlc;
+  DBuf<uint64_t> d_arr, d_Dp, d_ivF, d_thF;
+  DBuf<int4> d_ivh;
+  DBuf<int4> d_wl;
+  DBuf<int2> d_cinf;
+  DBuf<int64_t> d_gctx, d_ctsch;
   int Emax = 0;
   int64_t n_fallback = 0;  // graphs the last run replayed through kb_consensus
   // the commit stream in host memory (hge_batch_set_delivery), pooled like the device
@@ -1586,8 +1567,13 @@ struct hge_batch {
   bool no_pin = getenv("HGB_TEST_NO_PIN") != nullptr;  // test hook: take the copy path
   HostField<int32_t> h_ids, h_orr;
   HostField<int64_t> h_octs, h_counts;
-  Buf<int32_t> d_orr;  // the copy path's device side of rr / cts (ids and counts: d_order, d_counts)
-  Buf<int64_t> d_octs;
+  DBuf<int32_t> d_orr;  // the copy path's device side of rr / cts (ids and counts: d_order, d_counts)
+  DBuf<int64_t> d_octs;
+
+  // the stream drained before the members die
+  ~hge_batch() {
+    if (st) (void)hipStreamSynchronize(st);
+  }
 
   // sized from the staged pools; kept across runs
   void ensure_delivery() {
@@ -1610,36 +1596,6 @@ struct hge_batch {
     return h_ids.pinned && h_counts.pinned && (!(deliver & 2) || (h_orr.pinned && h_octs.pinned));
   }
 
-  void free_all() {
-    d_gd.free_();
-    h_ids.free_();
-    h_orr.free_();
-    h_octs.free_();
-    h_counts.free_();
-    d_orr.free_();
-    d_octs.free_();
-    for (auto* b : {&d_cr, &d_ix, &d_sp, &d_op, &d_oc, &d_ntx, &d_clen, &d_chain, &d_LA, &d_FDT, &d_FD, &d_round,
-                    &d_rr, &d_W, &d_WIX, &d_WFD, &d_rcnt, &d_ver, &d_thv, &d_th, &d_U, &d_Ur, &d_Ucp, &d_order,
-                    &d_krr, &d_kid})
-      b->free_();
-    for (auto* b : {&d_ts, &d_tsch, &d_calls, &d_cts, &d_counts, &d_scal, &d_kct}) b->free_();
-    for (auto* b : {&d_S, &d_ssb, &d_seeb, &d_ks0, &d_Sch}) b->free_();
-    d_ntxch.free_();
-    for (auto* b : {&d_roundch, &d_rrch, &d_rslot, &d_glist, &d_cg, &d_Rc, &d_rfirst, &d_rrank, &d_xcall, &d_gx, &d_nivl, &d_fsuf, &d_thp, &d_thR, &d_rcall, &d_bcnt,
-                    &d_boff, &d_wlc})
-      b->free_();
-    for (auto* b : {&d_arr, &d_Dp, &d_ivF, &d_thF}) b->free_();
-    d_ivh.free_();
-    d_wl.free_();
-    d_cinf.free_();
-    d_gctx.free_();
-    d_ctsch.free_();
-    d_coin.free_();
-    d_wit.free_();
-    d_WCOIN.free_();
-    d_fame.free_();
-  }
-
   // FromParentsLatest (hashgraph.go:366-396) and the index rule of the engine
   // (hge_engine.hip admit: index-lying events are refused, HGE_ERR_INDEX)
   int admit(Graph& G, const std::vector<int32_t>& last, const hge_event& e, int32_t sp, int32_t op) {
@@ -1659,8 +1615,8 @@ struct hge_batch {
   int add(const hge_event* ev, int64_t n_sub, const int64_t* cp, int64_t n_calls, int32_t* status) {
     for (int64_t c = 0; c < n_calls; c++)
       if (cp[c] < 1 || cp[c] > n_sub || (c > 0 && cp[c] <= cp[c - 1]))
-        throw BatchError{HGE_ERR_ARG, "hge_batch_add: call points must be strictly ascending within [1, n_sub]"};
-    if (n_sub >= INT32_MAX / 2) throw BatchError{HGE_ERR_ARG, "hge_batch_add: stream too long for a batch graph"};
+        throw Error{HGE_ERR_ARG, "hge_batch_add: call points must be strictly ascending within [1, n_sub]"};
+    if (n_sub >= INT32_MAX / 2) throw Error{HGE_ERR_ARG, "hge_batch_add: stream too long for a batch graph"};
     gs.emplace_back();
     Graph& G = gs.back();
     G.chain.assign(N, {});
@@ -1702,9 +1658,9 @@ struct hge_batch {
   }
 
   template <typename T>
-  void up(Buf<T>& b, const std::vector<T>& h) {
+  void up(DBuf<T>& b, const std::vector<T>& h) {
     b.need(h.size());
-    if (!h.empty()) BCHK(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    if (!h.empty()) HGE_HIPCHK(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
   }
 
   void stage() {
@@ -1712,7 +1668,7 @@ struct hge_batch {
       ensure_delivery();
       return;
     }
-    BCHK(hipSetDevice(device));
+    HGE_HIPCHK(hipSetDevice(device));
     const int G = (int)gs.size();
     hd.assign(G, GDesc{});
     Etot = Ktot = Rtot = 0;
@@ -1732,8 +1688,8 @@ struct hge_batch {
       Rtot += d.Rcap;
       for (int c = 0; c < N; c++) ccap = std::max(ccap, (int)gr.chain[c].size());
     }
-    if (Rtot >= INT32_MAX || Ktot >= INT32_MAX) throw BatchError{HGE_ERR_CAPACITY, "batch too large"};
-    if (ccap >= (1 << 24)) throw BatchError{HGE_ERR_CAPACITY, "batch graph with a chain of 2^24 events or more"};
+    if (Rtot >= INT32_MAX || Ktot >= INT32_MAX) throw Error{HGE_ERR_CAPACITY, "batch too large"};
+    if (ccap >= (1 << 24)) throw Error{HGE_ERR_CAPACITY, "batch graph with a chain of 2^24 events or more"};
     std::vector<int32_t> cr, ix, sp, op, oc, ntx, clen((size_t)G * N), chain((size_t)G * N * ccap, -1), cgv;
     Emax = 0;
     for (int g = 0; g < G; g++) {
@@ -1785,7 +1741,7 @@ struct hge_batch {
     up(d_ntxch, ntxch);
     up(d_cg, cgv);
     d_gd.need(G);
-    BCHK(hipMemcpyAsync(d_gd.p, hd.data(), sizeof(GDesc) * G, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_gd.p, hd.data(), sizeof(GDesc) * G, hipMemcpyHostToDevice, st));
     const size_t E1 = (size_t)std::max<int64_t>(Etot, 1);
     d_LA.need(E1 * N);
     d_FDT.need((size_t)G * N * N * ccap);
@@ -1845,7 +1801,7 @@ struct hge_batch {
     d_wlc.need(1);
     d_gctx.need(G);
     d_cinf.need(E1);
-    BCHK(hipStreamSynchronize(st));
+    HGE_HIPCHK(hipStreamSynchronize(st));
     ensure_delivery();
     staged = true;
   }
@@ -1936,7 +1892,7 @@ struct hge_batch {
   void launch(K kern, int G, const BT& t, int block = 64) {
     hipLaunchKernelGGL(kern, dim3(G), dim3(block), 0, st, t);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw BatchError{HGE_ERR_DEVICE, std::string("batch launch: ") + hipGetErrorString(e)};
+    if (e != hipSuccess) throw Error{HGE_ERR_DEVICE, std::string("batch launch: ") + hipGetErrorString(e)};
   }
 
   template <int NM, bool DLV>
@@ -1947,56 +1903,56 @@ struct hge_batch {
     if (G <= 2 * ncu) {
       if (Emax > 0) {
         hipLaunchKernelGGL(kb_levels, dim3((unsigned)((Emax + 255) / 256), (unsigned)G), dim3(256), 0, st, t);
-        BCHK(hipGetLastError());
+        HGE_HIPCHK(hipGetLastError());
       }
       // the columns split over two workgroups while both still get a CU of their own
       // (128 graphs: 0.46 -> 0.43 ms; at 256 graphs, two per CU, 0.49 -> 0.51; four
       // 8-column parts: 0.45 / 0.55)
       if (2 * G <= ncu) hipLaunchKernelGGL((kb_coords<NM, 512, true, 2>), dim3(G * 2), dim3(512), 0, st, t);
       else launch(kb_coords<NM, 1024, true>, G, t, 1024);
-      BCHK(hipGetLastError());
+      HGE_HIPCHK(hipGetLastError());
     } else {
       launch(kb_coords<NM, 512, false>, G, t, 512);
     }
-    BCHK(hipEventRecord(ev[1], st));
+    HGE_HIPCHK(hipEventRecord(ev[1], st));
     launch(kb_fd<NM>, G * N, t, 64 * (NM / FCW));
-    BCHK(hipEventRecord(ev[2], st));
+    HGE_HIPCHK(hipEventRecord(ev[2], st));
     launch(kb_fdrows<NM>, G * N, t, 256);  // rows for kb_front (kb_median reads the run layout)
-    BCHK(hipEventRecord(ev[3], st));
+    HGE_HIPCHK(hipEventRecord(ev[3], st));
     if (G > 2 * ncu) launch(kb_front<NM, 256>, G, t, 256);
     else if (G > ncu) launch(kb_front<NM, 512>, G, t, 512);
     else launch(kb_front<NM, 1024>, G, t, 1024);
-    BCHK(hipEventRecord(ev[4], st));
+    HGE_HIPCHK(hipEventRecord(ev[4], st));
     if (serial) {  // every graph through kb_consensus, after the run's readback
-      for (int k = 5; k < 9; k++) BCHK(hipEventRecord(ev[k], st));
+      for (int k = 5; k < 9; k++) HGE_HIPCHK(hipEventRecord(ev[k], st));
       return;
     }
     launch(kb_prep<NM>, G, t, 1024);
     if (G > 2 * ncu) hipLaunchKernelGGL((kb_pairs<NM, 2>), dim3(8, (unsigned)G), dim3(256), 0, st, t);
     else hipLaunchKernelGGL((kb_pairs<NM, 3>), dim3(8, (unsigned)G), dim3(256), 0, st, t);
-    BCHK(hipGetLastError());
-    BCHK(hipEventRecord(ev[5], st));
+    HGE_HIPCHK(hipGetLastError());
+    HGE_HIPCHK(hipEventRecord(ev[5], st));
     if (G > 2 * ncu) launch((kb_fold<NM, 2>), G, t, 64);
     else launch((kb_fold<NM, 3>), G, t, 64);
     launch(kb_theta<NM>, G, t, 256);
-    BCHK(hipEventRecord(ev[6], st));
+    HGE_HIPCHK(hipEventRecord(ev[6], st));
     if (Emax > 0) {
       hipLaunchKernelGGL(kb_receive<NM>, dim3((unsigned)N, (unsigned)G), dim3(256), 0, st, t);
-      BCHK(hipGetLastError());
+      HGE_HIPCHK(hipGetLastError());
       hipLaunchKernelGGL(kb_median<NM>, dim3((unsigned)(N * ((ccap + 255) / 256)), (unsigned)G), dim3(256), 0, st, t);
-      BCHK(hipGetLastError());
+      HGE_HIPCHK(hipGetLastError());
     }
-    BCHK(hipEventRecord(ev[7], st));
+    HGE_HIPCHK(hipEventRecord(ev[7], st));
     launch(kb_order_prep<NM>, G, t, 1024);
     // call buckets: up to 1,024 keys one wave each (a workgroup of four while the
     // batch has few buckets), larger ones a workgroup each
     const int nbk = (int)std::min<int64_t>(std::max<int64_t>(Ktot, 1), (int64_t)ncu * 16);
     if (Ktot > 16 * (int64_t)ncu) hipLaunchKernelGGL((kb_sort<64, 0, 1024, DLV>), dim3(nbk), dim3(64), 0, st, t, 0);
     else hipLaunchKernelGGL((kb_sort<256, 0, 1024, DLV>), dim3(nbk), dim3(256), 0, st, t, 0);
-    BCHK(hipGetLastError());
+    HGE_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL((kb_sort<256, 1024, 4096, DLV>), dim3(ncu), dim3(256), 0, st, t, 1);
-    BCHK(hipGetLastError());
-    BCHK(hipEventRecord(ev[8], st));
+    HGE_HIPCHK(hipGetLastError());
+    HGE_HIPCHK(hipEventRecord(ev[8], st));
   }
 
   int64_t run() {
@@ -2024,7 +1980,7 @@ struct hge_batch {
     seg(d_wlc.p, 4, 0);
     seg(d_gctx.p, (size_t)G * 8, 0);
     hipLaunchKernelGGL(kb_clear, dim3((unsigned)std::min<size_t>(2048, (E1 * 8 / 16 + 255) / 256 + 1)), dim3(256), 0, st, cl);
-    BCHK(hipGetLastError());
+    HGE_HIPCHK(hipGetLastError());
     BT t = tables();
     // delivery: the sorts and kb_consensus store the commit stream into mapped host
     // memory (the fallback pass below into the same slots); it is the host's after the
@@ -2038,25 +1994,25 @@ struct hge_batch {
       t.ord_rr = mode == 1 ? h_orr.dev : d_orr.p;
       t.ord_cts = mode == 1 ? h_octs.dev : d_octs.p;
     }
-    BCHK(hipEventRecord(ev[0], st));
+    HGE_HIPCHK(hipEventRecord(ev[0], st));
     const bool dlv = t.ord_rr != nullptr;  // the kernel instances that store rr / cts in commit order
     if (N <= 32) dlv ? run_stages<32, true>(G, t) : run_stages<32, false>(G, t);
     else dlv ? run_stages<64, true>(G, t) : run_stages<64, false>(G, t);
     h_scal.resize((size_t)G * 8);
-    BCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
-    BCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < NK; k++) BCHK(hipEventElapsedTime(&kms[k], ev[k], ev[k + 1]));
+    HGE_HIPCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
+    HGE_HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < NK; k++) HGE_HIPCHK(hipEventElapsedTime(&kms[k], ev[k], ev[k + 1]));
     // graphs the bulk fold could not hold: replayed by kb_consensus (their outputs untouched so far)
     std::vector<int32_t> fb;
     for (int g = 0; g < G; g++)
       if (serial || (h_scal[(size_t)g * 8 + 7] && !h_scal[(size_t)g * 8 + 6])) fb.push_back(g);
     n_fallback = (int64_t)fb.size();
     if (!fb.empty()) {
-      BCHK(hipMemcpyAsync(d_glist.p, fb.data(), fb.size() * 4, hipMemcpyHostToDevice, st));
+      HGE_HIPCHK(hipMemcpyAsync(d_glist.p, fb.data(), fb.size() * 4, hipMemcpyHostToDevice, st));
       t.glist = d_glist.p;
       const int F = (int)fb.size();
       float ms = 0;
-      BCHK(hipEventRecord(ev[7], st));
+      HGE_HIPCHK(hipEventRecord(ev[7], st));
       auto replay = [&](auto kern_off, auto kern_on) {
         dlv ? launch(kern_on, F, t, 256) : launch(kern_off, F, t, 256);
       };
@@ -2067,15 +2023,15 @@ struct hge_batch {
         if (F > 2 * ncu) replay(kb_consensus<64, 4, false>, kb_consensus<64, 4, true>);
         else replay(kb_consensus<64, 1, false>, kb_consensus<64, 1, true>);
       }
-      BCHK(hipEventRecord(ev[8], st));
-      BCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
-      BCHK(hipStreamSynchronize(st));
-      BCHK(hipEventElapsedTime(&ms, ev[7], ev[8]));
+      HGE_HIPCHK(hipEventRecord(ev[8], st));
+      HGE_HIPCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
+      HGE_HIPCHK(hipStreamSynchronize(st));
+      HGE_HIPCHK(hipEventElapsedTime(&ms, ev[7], ev[8]));
       kms[NK - 1] += ms;
     }
     if (dbg_on) {  // section cycles of kb_consensus, summed over the graphs
       std::vector<uint64_t> hd_((size_t)G * 8);
-      BCHK(hipMemcpy(hd_.data(), d_dbg.p, (size_t)G * 64, hipMemcpyDeviceToHost));
+      HGE_HIPCHK(hipMemcpy(hd_.data(), d_dbg.p, (size_t)G * 64, hipMemcpyDeviceToHost));
       double sum[5] = {};
       for (int g = 0; g < G; g++)
         for (int i = 0; i < 5; i++) sum[i] += (double)hd_[(size_t)g * 8 + i];
@@ -2085,15 +2041,15 @@ struct hge_batch {
     int64_t tot = 0;
     for (int g = 0; g < G; g++) {
       if (h_scal[(size_t)g * 8 + 6])
-        throw BatchError{HGE_ERR_INTERNAL, "batch graph " + std::to_string(g) + ": round capacity exceeded"};
+        throw Error{HGE_ERR_INTERNAL, "batch graph " + std::to_string(g) + ": round capacity exceeded"};
       tot += h_scal[(size_t)g * 8 + 4];
     }
     if (mode == 2) {  // no pinned memory: one pooled copy per field
-      BCHK(hipMemcpy(h_ids.h, d_order.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
-      BCHK(hipMemcpy(h_counts.h, d_counts.p, (size_t)Ktot * 8, hipMemcpyDeviceToHost));
+      HGE_HIPCHK(hipMemcpy(h_ids.h, d_order.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
+      HGE_HIPCHK(hipMemcpy(h_counts.h, d_counts.p, (size_t)Ktot * 8, hipMemcpyDeviceToHost));
       if (deliver & 2) {
-        BCHK(hipMemcpy(h_orr.h, d_orr.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
-        BCHK(hipMemcpy(h_octs.h, d_octs.p, (size_t)Etot * 8, hipMemcpyDeviceToHost));
+        HGE_HIPCHK(hipMemcpy(h_orr.h, d_orr.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
+        HGE_HIPCHK(hipMemcpy(h_octs.h, d_octs.p, (size_t)Etot * 8, hipMemcpyDeviceToHost));
       }
     }
     delivered = mode;
@@ -2104,14 +2060,14 @@ struct hge_batch {
 
   template <typename T>
   void down(T* host, const T* dev, size_t n) {
-    if (host && n) BCHK(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
+    if (host && n) HGE_HIPCHK(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
   }
 };
 
 #define BGUARD_BEGIN try {
 #define BGUARD_END(b)                 \
   }                                   \
-  catch (BatchError & e) {            \
+  catch (Error & e) {                 \
     (b)->err = e.msg;                 \
     return e.code;                    \
   }                                   \
@@ -2129,11 +2085,11 @@ int hge_batch_create(int32_t n_participants, int32_t device, hge_batch** out) {
   b->SM = 2 * n_participants / 3 + 1;  // hashgraph.go:78-80
   b->device = device;
   try {
-    BCHK(hipSetDevice(device));
-    BCHK(hipDeviceGetAttribute(&b->ncu, hipDeviceAttributeMultiprocessorCount, device));
-    BCHK(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
-    for (auto& e : b->ev) BCHK(hipEventCreate(&e));
-  } catch (BatchError& e) {
+    HGE_HIPCHK(hipSetDevice(device));
+    HGE_HIPCHK(hipDeviceGetAttribute(&b->ncu, hipDeviceAttributeMultiprocessorCount, device));
+    b->st.create();
+    for (auto& e : b->ev) e.create();
+  } catch (Error& e) {
     delete b;
     return e.code;
   }
@@ -2142,12 +2098,6 @@ int hge_batch_create(int32_t n_participants, int32_t device, hge_batch** out) {
 }
 
 void hge_batch_destroy(hge_batch* b) {
-  if (!b) return;
-  if (b->st) (void)hipStreamSynchronize(b->st);
-  b->free_all();
-  for (auto& e : b->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (b->st) (void)hipStreamDestroy(b->st);
   delete b;
 }
 
@@ -2158,7 +2108,7 @@ int hge_batch_add(hge_batch* b, const hge_event* ev, int64_t n_sub, const int64_
   if (!b) return HGE_ERR_ARG;
   BGUARD_BEGIN
   if (n_sub < 0 || (n_sub > 0 && !ev) || n_calls < 0 || (n_calls > 0 && !call_points))
-    throw BatchError{HGE_ERR_ARG, "hge_batch_add: bad argument"};
+    throw Error{HGE_ERR_ARG, "hge_batch_add: bad argument"};
   const int g = b->add(ev, n_sub, call_points, n_calls, status_out);
   if (graph_out) *graph_out = g;
   return HGE_OK;
@@ -2201,7 +2151,7 @@ int hge_batch_results(hge_batch* b, int32_t g, int32_t* order, int64_t* counts, 
                       int32_t* rr, int64_t* cts, int8_t* fame, int32_t* undetermined) {
   if (!b || g < 0 || g >= (int)b->gs.size()) return HGE_ERR_ARG;
   BGUARD_BEGIN
-  if (!b->ran) throw BatchError{HGE_ERR_ARG, "hge_batch_results: no replay yet (hge_batch_run)"};
+  if (!b->ran) throw Error{HGE_ERR_ARG, "hge_batch_results: no replay yet (hge_batch_run)"};
   const GDesc& d = b->hd[g];
   const int64_t* s = &b->h_scal[(size_t)g * 8];
   const int N = b->N;

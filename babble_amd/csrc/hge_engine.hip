@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/hge.h"
+#include "hge_hip.h"
 #include "hge_plan.h"
 #include "hge_kernels.hip"
 #include "hge_median_rows.hip"
@@ -37,14 +38,6 @@
 
 using namespace hge;
 
-#define HIPCHK(x)                                                                    \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      throw EngineError(HGE_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    }                                                                                \
-  } while (0)
-
 // every launch is checked: a launch the runtime refuses (e.g. too much LDS)
 // must fail the call, never leave a table silently unwritten
 // KLAUNCH_AS: a kernel pointer chosen at run time (WalkKernels) under its instantiation's name
@@ -55,7 +48,7 @@ using namespace hge;
     hipLaunchKernelGGL(kern, __VA_ARGS__);                                             \
     const hipError_t le_ = hipGetLastError();                                          \
     if (le_ != hipSuccess)                                                             \
-      throw EngineError(HGE_ERR_DEVICE, std::string("launch ") + name + ": " + hipGetErrorString(le_)); \
+      throw Error(HGE_ERR_DEVICE, std::string("launch ") + name + ": " + hipGetErrorString(le_)); \
     prof_end();                                                                        \
   } while (0)
 #define KLAUNCH(kern, ...) KLAUNCH_AS(#kern, kern, __VA_ARGS__)
@@ -83,50 +76,12 @@ using namespace hge;
       SHAPE(4, __VA_ARGS__);                                       \
       break;                                                       \
     default:                                                       \
-      throw EngineError(HGE_ERR_INTERNAL, "unsupported N");        \
+      throw Error(HGE_ERR_INTERNAL, "unsupported N");              \
   }
 #define KLAUNCH_NW(nw, SHAPE, ...) NW_SWITCH_(nw, case 1 : SHAPE(1, __VA_ARGS__); break;, SHAPE, __VA_ARGS__)
 #define KLAUNCH_NW2(nw, SHAPE, ...) NW_SWITCH_(nw, , SHAPE, __VA_ARGS__)
 
 namespace {
-
-struct EngineError {
-  int code;
-  std::string msg;
-  EngineError(int c, std::string m) : code(c), msg(std::move(m)) {}
-};
-
-template <typename T>
-struct DBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  void free_() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  // grow without preserving contents
-  void need(size_t m) {
-    if (m <= n) return;
-    free_();
-    size_t cap = std::max<size_t>(m, 64);
-    HIPCHK(hipMalloc(&p, cap * sizeof(T)));
-    n = cap;
-  }
-  // grow preserving contents [0, keep)
-  void grow_keep(size_t m, size_t keep, hipStream_t st, int fill_byte = -1) {
-    if (m <= n) return;
-    size_t cap = std::max<size_t>(m, n + n / 2);
-    T* q = nullptr;
-    HIPCHK(hipMalloc(&q, cap * sizeof(T)));
-    if (fill_byte >= 0) HIPCHK(hipMemsetAsync(q, fill_byte, cap * sizeof(T), st));
-    if (p && keep) HIPCHK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    free_();
-    p = q;
-    n = cap;
-  }
-};
 
 inline int div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static const int32_t kInf = INF32;
@@ -136,7 +91,8 @@ static const int32_t kInf = INF32;
 struct hge_engine {
   int N = 0, NW = 1, SM = 1;
   int device = 0;
-  hipStream_t st = nullptr;
+  // declared before every buffer and event, so destroyed after them
+  Stream st;
   std::string err;
 
   // ---- host control state ----
@@ -180,28 +136,22 @@ struct hge_engine {
   // log's last cons_pin_n ids.  Readers take it from there (hge_replay_order: a view,
   // hge_replay_fetch: one copy); the log's vector gets them on first use
   // (consensus_sync), outside the replay.
-  int32_t* pin_ord = nullptr;
+  PBuf<int32_t> pin_ord;
   int32_t* pin_ord_dev = nullptr;  // its device-side address (the sorts write there)
-  size_t pin_ord_cap = 0;
   int64_t cons_pin_n = 0;
   bool lazy_order = false;
   int64_t consensus_size() const { return (int64_t)consensus.size() + cons_pin_n; }
   void consensus_sync() {
     if (!cons_pin_n) return;
-    consensus.insert(consensus.end(), pin_ord, pin_ord + cons_pin_n);
+    consensus.insert(consensus.end(), pin_ord.p, pin_ord.p + cons_pin_n);
     cons_pin_n = 0;
   }
   void ensure_pin_ord(size_t n) {
-    if (n <= pin_ord_cap && pin_ord) return;
+    if (n <= pin_ord.n && pin_ord.p) return;
     consensus_sync();
-    if (pin_ord) HIPCHK(hipHostFree(pin_ord));
-    pin_ord = nullptr;
     pin_ord_dev = nullptr;
-    pin_ord_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&pin_ord, std::max<size_t>(n, 1) * 4, hipHostMallocDefault));
-    pin_ord_cap = std::max<size_t>(n, 1);
-    void* dp = nullptr;
-    pin_ord_dev = hipHostGetDevicePointer(&dp, pin_ord, 0) == hipSuccess ? (int32_t*)dp : nullptr;
+    pin_ord.need(std::max<size_t>(n, 1));
+    pin_ord_dev = PinnedMem::device_ptr(pin_ord.p);
   }
   int64_t n_und = 0;
 
@@ -248,7 +198,7 @@ struct hge_engine {
   DBuf<int32_t> s_lwpos, s_lwrisky;
   int ncu_cache = 0;
   int n_cu() {
-    if (!ncu_cache) HIPCHK(hipDeviceGetAttribute(&ncu_cache, hipDeviceAttributeMultiprocessorCount, device));
+    if (!ncu_cache) HGE_HIPCHK(hipDeviceGetAttribute(&ncu_cache, hipDeviceAttributeMultiprocessorCount, device));
     return ncu_cache;
   }
   DBuf<int32_t> d_FDTD;  // N > 16: timestamp offsets at the FD positions (the wide median)
@@ -283,10 +233,10 @@ struct hge_engine {
   DBuf<int32_t> s_cn;
   uint32_t coop_epoch = 0;
 
-  hipEvent_t ev[8] = {};
+  Event ev[8];
   // per-kernel HIP-event timing on the engine stream (hge_set_profiling)
   bool prof_on = false;
-  std::vector<hipEvent_t> prof_pool;
+  std::vector<Event> prof_pool;
   std::vector<std::pair<std::string, int>> prof_rec;
   std::vector<std::string> prof_names;
   std::vector<double> prof_ms;
@@ -352,9 +302,9 @@ struct hge_engine {
     NW = (N + 63) / 64;
     SM = 2 * N / 3 + 1;  // hashgraph.go:78-80
     device = dev;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    HGE_HIPCHK(hipSetDevice(device));
+    st.create();
+    for (auto& e : ev) e.create();
     chain_len.assign(N, 0);
     chain_last.assign(N, -1);
     h_chain.assign(N, {});
@@ -378,23 +328,22 @@ struct hge_engine {
     if (!prof_on) return;
     const int slot = (int)prof_rec.size() * 2;
     while ((int)prof_pool.size() < slot + 2) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      prof_pool.push_back(e);
+      prof_pool.emplace_back();
+      prof_pool.back().create();
     }
-    HIPCHK(hipEventRecord(prof_pool[slot], st));
+    HGE_HIPCHK(hipEventRecord(prof_pool[slot], st));
     prof_rec.push_back({name, slot});
   }
   void prof_end() {
     if (!prof_on) return;
-    HIPCHK(hipEventRecord(prof_pool[prof_rec.back().second + 1], st));
+    HGE_HIPCHK(hipEventRecord(prof_pool[prof_rec.back().second + 1], st));
   }
   void prof_collect() {
     if (prof_rec.empty()) return;
-    HIPCHK(hipStreamSynchronize(st));
+    HGE_HIPCHK(hipStreamSynchronize(st));
     for (auto& r : prof_rec) {
       float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, prof_pool[r.second], prof_pool[r.second + 1]));
+      HGE_HIPCHK(hipEventElapsedTime(&ms, prof_pool[r.second], prof_pool[r.second + 1]));
       size_t k = 0;
       while (k < prof_names.size() && prof_names[k] != r.first) k++;
       if (k == prof_names.size()) {
@@ -415,7 +364,7 @@ struct hge_engine {
     if (!dbg_on) return nullptr;
     if (!s_dbg.p) {
       s_dbg.need(16);
-      HIPCHK(hipMemset(s_dbg.p, 0, 16 * 8));
+      HGE_HIPCHK(hipMemsetAsync(s_dbg.p, 0, 16 * 8, st));
     }
     return s_dbg.p;
   }
@@ -428,7 +377,9 @@ struct hge_engine {
     fprintf(stderr, "\n");
   }
 
-  void destroy() {
+  // only what must come before the members die: the stream drained (then the buffers and
+  // events free themselves, the stream last) and the HGE_HOST_PHASES line
+  ~hge_engine() {
     if (st) (void)hipStreamSynchronize(st);
     if (getenv("HGE_HOST_PHASES") && hp.calls) {
       const double c = (double)hp.calls;
@@ -438,73 +389,6 @@ struct hge_engine {
               (long long)hp.calls, hp.launches / c, hp.copies / c, hp.insert_ns / c / 1e3, hp.call_ns / c / 1e3,
               hp.wait_ns / c / 1e3);
     }
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : prof_pool) (void)hipEventDestroy(e);
-    prof_pool.clear();
-    DBuf<int32_t>* i32s[] = {&d_creator, &d_index,  &d_sp,    &d_op,     &d_ntx,     &d_round,
-                             &d_rr,      &d_und,    &d_chain, &d_LA,     &d_FD,      &d_C,
-                             &d_W,       &d_rcnt,   &d_minw,  &s_small,  &s_newwit,  &s_LCR,
-                             &s_clast,   &s_segcnt, &s_segcall, &s_seground, &s_theta,
-                             &s_recv,    &s_rr,     &s_bpos,  &s_fund,   &s_upos,    &s_vis,
-                             &s_und2,    &s_part,   &s_fst,    &d_FSS,
-                             &d_FDT,     &s_chg,    &s_bar,   &s_bseg,   &s_kctl,    &s_cctl,
-                             &s_out,     &s_hn,     &s_hres,  &s_dirty,  &d_WLA,     &s_lwpos,
-                             &s_lwrisky, &s_src,    &s_relay, &s_rfail,  &s_fdlo};
-    for (auto* b : i32s) b->free_();
-    s_dec2.free_();
-    s_lwplan.free_();
-    d_WLR.free_();
-    s_xbuf.free_();
-    s_sord.free_();
-    s_soff.free_();
-    s_lwsum.free_();
-    s_lwinit.free_();
-    d_ts.free_();
-    d_FDTD.free_();
-    d_FDTW.free_();
-    d_cts.free_();
-    s_cts.free_();
-    d_S.free_();
-    d_ssb.free_();
-    d_seeb.free_();
-    s_H.free_();
-    s_wdbg.free_();
-    s_segfws.free_();
-    d_coin.free_();
-    d_wit.free_();
-    d_fame.free_();
-    s_dec.free_();
-    s_decbit.free_();
-    s_segdec.free_();
-    s_keys.free_();
-    s_keys2.free_();
-    d_opcp.free_();
-    d_tsch.free_();
-    d_LA16.free_();
-    d_ssc.free_();
-    s_gran.free_();
-    s_cH.free_();
-    s_cS.free_();
-    s_cT.free_();
-    s_cM.free_();
-    s_cn.free_();
-    s_mb.free_();
-    s_wpaths.free_();
-    s_spaths.free_();
-    s_hist.free_();
-    s_hstate.free_();
-    s_hssc.free_();
-    if (pin) (void)hipHostFree(pin);
-    pin = nullptr;
-    pin_cap = pin_used = 0;
-    if (pin_ord) (void)hipHostFree(pin_ord);
-    pin_ord = nullptr;
-    pin_ord_dev = nullptr;
-    pin_ord_cap = 0;
-    cons_pin_n = 0;
-    if (st) (void)hipStreamDestroy(st);
-    st = nullptr;
   }
 
   void ensure_events(int64_t m) {
@@ -526,109 +410,44 @@ struct hge_engine {
     Ecap = cap;
   }
 
-  // chain-major tables [N][ccap][N]: grow to nc positions per chain, keeping contents
-  // rowmajor: [N][ccap][N] (LA, FD, FSS); else [N][N][ccap] (LAT, FDT)
-  template <typename T>
-  void grow_chain_table(DBuf<T>& b, int64_t nc, bool keep, bool rowmajor = true) {
-    T* q = nullptr;
-    HIPCHK(hipMalloc(&q, sizeof(T) * (size_t)N * nc * N));
-    const size_t rows = rowmajor ? N : (size_t)N * N, w = rowmajor ? N : 1;
-    if (keep && ccap > 0 && b.p)
-      HIPCHK(hipMemcpy2DAsync(q, sizeof(T) * nc * w, b.p, sizeof(T) * ccap * w,
-                              sizeof(T) * ccap * w, rows, hipMemcpyDeviceToDevice, st));
-    sync();
-    b.free_();
-    b.p = q;
-    b.n = (size_t)N * nc * N;
-  }
-
+  // The chain tables hold ccap positions per row: grown to nc positions one table at a
+  // time (the peak is one table twice), each row copied to the head of its longer row
+  // (hge::Buf::regrow_rows).  Every call states its table's geometry: rows, bytes per
+  // position of a row, total bytes, the resulting n.  A failure between two tables leaves
+  // them at different row pitches while ccap is unchanged.
   void ensure_ccap(int64_t m) {
     if (m <= ccap) return;
     // a multiple of 64 positions: the uint16 run table's rows stay 8-byte aligned
-    int64_t nc = (std::max<int64_t>(m, (int64_t)ccap + ccap / 2) + 63) & ~(int64_t)63;
-    int32_t* chain = nullptr;
-    HIPCHK(hipMalloc(&chain, sizeof(int32_t) * N * nc));
-    HIPCHK(hipMemsetAsync(chain, 0xFF, sizeof(int32_t) * N * nc, st));
-    if (ccap > 0)
-      HIPCHK(hipMemcpy2DAsync(chain, sizeof(int32_t) * nc, d_chain.p, sizeof(int32_t) * ccap,
-                              sizeof(int32_t) * ccap, N, hipMemcpyDeviceToDevice, st));
-    sync();
-    d_chain.free_();
-    d_chain.p = chain;
-    d_chain.n = (size_t)N * nc;
-    int2* opcp = nullptr;
-    HIPCHK(hipMalloc(&opcp, sizeof(int2) * N * nc));
-    if (ccap > 0)
-      HIPCHK(hipMemcpy2DAsync(opcp, sizeof(int2) * nc, d_opcp.p, sizeof(int2) * ccap,
-                              sizeof(int2) * ccap, N, hipMemcpyDeviceToDevice, st));
-    sync();
-    d_opcp.free_();
-    d_opcp.p = opcp;
-    d_opcp.n = (size_t)N * nc;
-    int64_t* tsch = nullptr;
-    HIPCHK(hipMalloc(&tsch, sizeof(int64_t) * N * nc));
-    if (ccap > 0)
-      HIPCHK(hipMemcpy2DAsync(tsch, sizeof(int64_t) * nc, d_tsch.p, sizeof(int64_t) * ccap,
-                              sizeof(int64_t) * ccap, N, hipMemcpyDeviceToDevice, st));
-    sync();
-    d_tsch.free_();
-    d_tsch.p = tsch;
-    d_tsch.n = (size_t)N * nc;
-    if (!sweep16()) grow_chain_table(d_LA, nc, true);
+    const int64_t nc = (std::max<int64_t>(m, (int64_t)ccap + ccap / 2) + 63) & ~(int64_t)63;
+    const size_t n = N, oc = ccap, c = nc;
+    auto regrow = [&](auto& b, size_t rows, size_t pos_bytes, size_t total_bytes, size_t n_after, int fill = -1) {
+      b.regrow_rows(rows, pos_bytes * oc, pos_bytes * c, total_bytes, n_after, ccap > 0, st, fill);
+      sync();  // a table regrown is a host wait (hge_host_syncs); queued downloads land
+    };
+    regrow(d_chain, n, sizeof(int32_t), sizeof(int32_t) * n * c, n * c, 0xFF);
+    regrow(d_opcp, n, sizeof(int2), sizeof(int2) * n * c, n * c);
+    regrow(d_tsch, n, sizeof(int64_t), sizeof(int64_t) * n * c, n * c);
+    // row-major [N][ccap][N]: a chain's block is one row
+    if (!sweep16()) regrow(d_LA, n, sizeof(int32_t) * n, sizeof(int32_t) * n * c * n, n * c * n);
     if (N > 32) {  // (kept across a switch to int32: a later stream starts packed again)
-      const size_t w = (size_t)(N + 1) / 2;
-      uint32_t* q = nullptr;
-      HIPCHK(hipMalloc(&q, sizeof(uint32_t) * (size_t)N * nc * w));
-      if (ccap > 0 && d_LA16.p)
-        HIPCHK(hipMemcpy2DAsync(q, sizeof(uint32_t) * nc * w, d_LA16.p, sizeof(uint32_t) * ccap * w,
-                                sizeof(uint32_t) * ccap * w, N, hipMemcpyDeviceToDevice, st));
-      sync();
-      d_LA16.free_();
-      d_LA16.p = q;
-      d_LA16.n = (size_t)N * nc * w;
+      const size_t w = (n + 1) / 2;
+      regrow(d_LA16, n, sizeof(uint32_t) * w, sizeof(uint32_t) * n * c * w, n * c * w);
     }
-    if (fdt16()) {  // uint16 FD rows: a chain's block is ccap * N halves
-      int32_t* q = nullptr;
-      HIPCHK(hipMalloc(&q, sizeof(uint16_t) * (size_t)N * nc * N));
-      if (ccap > 0 && d_FD.p)
-        HIPCHK(hipMemcpy2DAsync(q, 2 * (size_t)nc * N, d_FD.p, 2 * (size_t)ccap * N, 2 * (size_t)ccap * N, N,
-                                hipMemcpyDeviceToDevice, st));
-      sync();
-      d_FD.free_();
-      d_FD.p = q;
-      d_FD.n = (size_t)N * nc * N / 2;
-    } else {
-      grow_chain_table(d_FD, nc, true);
-    }
+    if (fdt16())  // uint16 FD rows: a chain's block is ccap * N halves
+      regrow(d_FD, n, sizeof(uint16_t) * n, sizeof(uint16_t) * n * c * n, n * c * n / 2);
+    else
+      regrow(d_FD, n, sizeof(int32_t) * n, sizeof(int32_t) * n * c * n, n * c * n);
     if (N > 16) {  // FD timestamp rows below a batch's qlo are kept
-      grow_chain_table(d_FDTD, nc, true);
-      const size_t NT = (size_t)(N + 63) / 64;
-      uint8_t* q = nullptr;
-      HIPCHK(hipMalloc(&q, (size_t)N * nc * NT));
-      if (ccap > 0 && d_FDTW.p)
-        HIPCHK(hipMemcpy2DAsync(q, nc * NT, d_FDTW.p, (size_t)ccap * NT, (size_t)ccap * NT, N,
-                                hipMemcpyDeviceToDevice, st));
-      sync();
-      d_FDTW.free_();
-      d_FDTW.p = q;
-      d_FDTW.n = (size_t)N * nc * NT;
+      regrow(d_FDTD, n, sizeof(int32_t) * n, sizeof(int32_t) * n * c * n, n * c * n);
+      const size_t NT = (n + 63) / 64;
+      regrow(d_FDTW, n, NT, n * c * NT, n * c * NT);
     }
     // first-strong-seer rows (N <= 32): int32 rows of N, or uint16 rows padded to
     // 16/32 columns for the LDS walk; rebuilt from the frontier on, never kept
-    if (N <= 32) d_FSS.need((size_t)N * nc * std::max(N, 16));
-    if (fdt16()) {  // uint16 runs: rows of ccap halves (the buffer keeps int32 capacity)
-      int32_t* q = nullptr;
-      HIPCHK(hipMalloc(&q, sizeof(int32_t) * (size_t)N * nc * N));
-      if (ccap > 0 && d_FDT.p)
-        HIPCHK(hipMemcpy2DAsync(q, 2 * (size_t)nc, d_FDT.p, 2 * (size_t)ccap, 2 * (size_t)ccap, (size_t)N * N,
-                                hipMemcpyDeviceToDevice, st));
-      sync();
-      d_FDT.free_();
-      d_FDT.p = q;
-      d_FDT.n = (size_t)N * nc * N;
-    } else {
-      grow_chain_table(d_FDT, nc, true, false);  // persistent: FD in run layout
-    }
+    if (N <= 32) d_FSS.need(n * c * std::max(N, 16));
+    // persistent: FD in run layout [N][N][ccap]; uint16 runs are rows of ccap halves (the
+    // buffer keeps int32 capacity)
+    regrow(d_FDT, n * n, fdt16() ? sizeof(uint16_t) : sizeof(int32_t), sizeof(int32_t) * n * c * n, n * c * n);
     ccap = (int)nc;
   }
 
@@ -685,7 +504,7 @@ struct hge_engine {
     w32_done = 0;
     chain_limit = chain_limit0;
     reset_rounds();
-    HIPCHK(hipMemsetAsync(d_chain.p, 0xFF, (size_t)N * ccap * 4, st));
+    HGE_HIPCHK(hipMemsetAsync(d_chain.p, 0xFF, (size_t)N * ccap * 4, st));
     sync();
   }
 
@@ -789,7 +608,7 @@ struct hge_engine {
       // pinned arena, unpacked by the coordinate step's k_chain_fill (eight copies
       // from pageable memory were ~25 us of an online call)
       std::vector<UpEv> up((size_t)m);
-      if (up_n0 >= 0) throw EngineError(HGE_ERR_INTERNAL, "packed upload pending twice");
+      if (up_n0 >= 0) throw Error(HGE_ERR_INTERNAL, "packed upload pending twice");
       for (int64_t i = 0; i < m; i++) {
         UpEv& r = up[(size_t)i];
         const size_t x = (size_t)(a + i);
@@ -809,14 +628,14 @@ struct hge_engine {
       n_dev = n_events;
       return;
     }
-    HIPCHK(hipMemcpyAsync(d_creator.p + a, h_creator.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_index.p + a, h_index.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sp.p + a, h_sp.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_op.p + a, h_op.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ntx.p + a, h_ntx.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ts.p + a, h_ts.data() + a, 8 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_S.p + 4 * a, h_S.data() + 4 * a, 32 * m, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_coin.p + a, h_coin.data() + a, m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_creator.p + a, h_creator.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_index.p + a, h_index.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_sp.p + a, h_sp.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_op.p + a, h_op.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_ntx.p + a, h_ntx.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_ts.p + a, h_ts.data() + a, 8 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_S.p + 4 * a, h_S.data() + 4 * a, 32 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_coin.p + a, h_coin.data() + a, m, hipMemcpyHostToDevice, st));
     n_dev = n_events;
   }
 
@@ -834,8 +653,8 @@ struct hge_engine {
   // a pinned arena instead: uploads are enqueued without waiting, downloads are
   // queued and land in their host destinations at the next sync(), which also
   // recycles the arena (everything enqueued before it has completed).
-  char* pin = nullptr;
-  size_t pin_cap = 0, pin_used = 0;
+  PBuf<char> pin;
+  size_t pin_used = 0;
   struct Pending {
     void* dst;
     size_t off, bytes;
@@ -844,16 +663,11 @@ struct hge_engine {
 
   char* pin_take(size_t bytes) {
     const size_t need = (bytes + 255) & ~(size_t)255;
-    if (pin_used + need > pin_cap) {
+    if (pin_used + need > pin.n) {
       sync();
-      if (need > pin_cap) {
-        if (pin) HIPCHK(hipHostFree(pin));
-        pin = nullptr;
-        pin_cap = std::max<size_t>(need, std::max<size_t>(2 * pin_cap, 1 << 16));
-        HIPCHK(hipHostMalloc((void**)&pin, pin_cap, hipHostMallocDefault));
-      }
+      if (need > pin.n) pin.need(std::max<size_t>(need, std::max<size_t>(2 * pin.n, 1 << 16)));
     }
-    char* q = pin + pin_used;
+    char* q = pin.p + pin_used;
     pin_used += need;
     return q;
   }
@@ -862,22 +676,22 @@ struct hge_engine {
     char* q = pin_take(bytes);
     memcpy(q, host, bytes);
     hp.copies++;
-    HIPCHK(hipMemcpyAsync(dev, q, bytes, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(dev, q, bytes, hipMemcpyHostToDevice, st));
   }
   void d2h(void* host, const void* dev, size_t bytes) {
     if (!bytes) return;
     char* q = pin_take(bytes);
     hp.copies++;
-    HIPCHK(hipMemcpyAsync(q, dev, bytes, hipMemcpyDeviceToHost, st));
-    pending.push_back({host, (size_t)(q - pin), bytes});
+    HGE_HIPCHK(hipMemcpyAsync(q, dev, bytes, hipMemcpyDeviceToHost, st));
+    pending.push_back({host, (size_t)(q - pin.p), bytes});
   }
   // download into the arena itself: the returned offset stays readable after the
   // next sync() until the arena is used again (no second host copy)
   size_t d2h_pinned(const void* dev, size_t bytes) {
     char* q = pin_take(bytes);
     if (bytes) hp.copies++;
-    if (bytes) HIPCHK(hipMemcpyAsync(q, dev, bytes, hipMemcpyDeviceToHost, st));
-    return (size_t)(q - pin);
+    if (bytes) HGE_HIPCHK(hipMemcpyAsync(q, dev, bytes, hipMemcpyDeviceToHost, st));
+    return (size_t)(q - pin.p);
   }
   int64_t n_syncs = 0;  // host waits on the stream (hge_host_syncs)
   // where an online call's host time goes (HGE_HOST_PHASES=1: printed at destroy):
@@ -892,9 +706,9 @@ struct hge_engine {
   void sync() {
     n_syncs++;
     const int64_t w0 = now_ns();
-    HIPCHK(hipStreamSynchronize(st));
+    HGE_HIPCHK(hipStreamSynchronize(st));
     hp.wait_ns += now_ns() - w0;
-    for (const Pending& pd : pending) memcpy(pd.dst, pin + pd.off, pd.bytes);
+    for (const Pending& pd : pending) memcpy(pd.dst, pin.p + pd.off, pd.bytes);
     pending.clear();
     pin_used = 0;
   }
@@ -1001,14 +815,14 @@ struct hge_engine {
       return s_xbuf.p;
     }
     void* b = nullptr;
-    if (!x_fn) throw EngineError(HGE_ERR_ARG, "split replay: no exchange (hge_split_exchange)");
-    if (x_fn(x_ctx, 0, bytes, &b) != 0 || !b) throw EngineError(HGE_ERR_DEVICE, "split exchange: no buffer");
+    if (!x_fn) throw Error(HGE_ERR_ARG, "split replay: no exchange (hge_split_exchange)");
+    if (x_fn(x_ctx, 0, bytes, &b) != 0 || !b) throw Error(HGE_ERR_DEVICE, "split exchange: no buffer");
     return b;
   }
   void x_gather(int64_t bytes, void* b) {
     sync();
     if (emulating()) return;  // the caller fills the other parts' slots from the record
-    if (x_fn(x_ctx, 1, bytes, &b) != 0) throw EngineError(HGE_ERR_DEVICE, "split exchange failed");
+    if (x_fn(x_ctx, 1, bytes, &b) != 0) throw Error(HGE_ERR_DEVICE, "split exchange failed");
   }
   // fame rounds of part g: the pr_* indices [win_lo, win_hi) whose round's first witness
   // lies in the part's events (h_minw is ascending in the round)
@@ -1095,7 +909,7 @@ struct hge_engine {
     }
     // the packed event records (an online call's upload) ride in the same copy
     const bool packed = up_n0 == s.n0 && up_n1 == s.n1;
-    if (packed && h_up.empty()) throw EngineError(HGE_ERR_INTERNAL, "packed upload without records");
+    if (packed && h_up.empty()) throw Error(HGE_ERR_INTERNAL, "packed upload without records");
     static_assert(sizeof(UpEv) % 4 == 0, "records are whole words");
     static_assert(sizeof(hge_plan::Seg) == sizeof(int2), "the kernels read segments as int2");
     const hge_plan::CoordsCtl L =
@@ -1175,7 +989,7 @@ struct hge_engine {
         // are recomputed from scratch.
         frontier_fallback = true;
         n_frontier_fallbacks++;
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(d_C.p + (size_t)R * N), INF32, (size_t)(Rcap - R) * N, st));
+        HGE_HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(d_C.p + (size_t)R * N), INF32, (size_t)(Rcap - R) * N, st));
       } else if (o == RoundsOutcome::Grow) {
         ensure_rcap((int64_t)Rcap * 2);
       } else {
@@ -1288,7 +1102,7 @@ struct hge_engine {
     const int Hcap = hc ? std::max(2, atoi(hc)) : std::max(256, std::min(Rcap, 3 * (Rcap / nw) + 256));
     if ((size_t)nw * Hcap * N > s_H.n) {
       s_H.need((size_t)nw * Hcap * N);  // epoch 0 never matches a launch's tag
-      HIPCHK(hipMemsetAsync(s_H.p, 0, s_H.n * sizeof(uint64_t), st));
+      HGE_HIPCHK(hipMemsetAsync(s_H.p, 0, s_H.n * sizeof(uint64_t), st));
     }
     s_hres.need(4 * (size_t)nw + 1);
     s_hn.need(2 * (size_t)nw);
@@ -1400,7 +1214,7 @@ struct hge_engine {
     const int sbs = N > 64 ? 1024 : COOP_SPEC_BS;
     if (sbs != coop_spec_bs) {
       coop_spec_bs = sbs;
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&coop_spec_nb, coop_spec_fn(), sbs, 0));
+      HGE_HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&coop_spec_nb, coop_spec_fn(), sbs, 0));
     }
     const int cap = (int)std::min<int64_t>(16, (int64_t)coop_spec_nb * coop_ncu / N);
     const char* ev = getenv("HGE_COOP_WALKERS");
@@ -1432,12 +1246,12 @@ struct hge_engine {
     for (auto& e : resident_nb)
       if (e.first.first == fn && e.first.second == bs) nb = e.second;
     if (nb < 0) {
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, bs, 0));
+      HGE_HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, bs, 0));
       resident_nb.push_back({{fn, bs}, nb});
     }
     const int64_t blocks = (int64_t)grid.x * grid.y * grid.z;
     if ((int64_t)nb * n_cu() < blocks)
-      throw EngineError(HGE_ERR_DEVICE, "frontier grid of " + std::to_string(blocks) + " workgroups x " +
+      throw Error(HGE_ERR_DEVICE, "frontier grid of " + std::to_string(blocks) + " workgroups x " +
                                             std::to_string(bs) + " threads cannot be co-resident (" +
                                             std::to_string(nb) + " per CU x " + std::to_string(n_cu()) + " CUs)");
     return hipLaunchKernel(fn, grid, block, args, 0, st);
@@ -1481,7 +1295,7 @@ struct hge_engine {
     // admission switches the engine to int32 positions (to_wide32) before a chain
     // passes 65,534 events, so this packed walk never sees one; the check guards it
     if (s.maxlen >= 0xFFFF)
-      throw EngineError(HGE_ERR_INTERNAL, "packed rounds walk reached a chain past 65,534 events");
+      throw Error(HGE_ERR_INTERNAL, "packed rounds walk reached a chain past 65,534 events");
     const bool from_zero = s.fresh && rlo == 0 && Rprev == 0;
     if (ext_on && from_zero && install_ext_rows(s, rlo)) return {};
     Walk w;
@@ -1501,9 +1315,9 @@ struct hge_engine {
   bool coop_resident() {
     if (coop_checked) return true;
     int nb = 0, ncu = 0, coop = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_rounds_coop, COOP_BS, 0));
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-    HIPCHK(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, device));
+    HGE_HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_rounds_coop, COOP_BS, 0));
+    HGE_HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    HGE_HIPCHK(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, device));
     if (!coop || (int64_t)nb * ncu < N) return false;
     coop_nb = nb;
     coop_ncu = ncu;
@@ -1552,13 +1366,13 @@ struct hge_engine {
       clear = true;
     }
     if (clear) {
-      HIPCHK(hipMemsetAsync(s_cH.p, 0, s_cH.n * sizeof(uint64_t), st));
-      HIPCHK(hipMemsetAsync(s_cT.p, 0, s_cT.n * sizeof(uint64_t), st));
+      HGE_HIPCHK(hipMemsetAsync(s_cH.p, 0, s_cH.n * sizeof(uint64_t), st));
+      HGE_HIPCHK(hipMemsetAsync(s_cT.p, 0, s_cT.n * sizeof(uint64_t), st));
     }
     s_cS.need(nh * NW);
     s_cM.need(nw);
     s_cn.need(2 * (size_t)nw + 1);
-    HIPCHK(hipMemsetAsync(s_cM.p, 0xFF, (size_t)nw * sizeof(uint64_t), st));
+    HGE_HIPCHK(hipMemsetAsync(s_cM.p, 0xFF, (size_t)nw * sizeof(uint64_t), st));
     int64_t nev = 0;
     for (int c = 0; c < N; c++) nev += chain_len[c];
     // guesses (measured over seeds 1-3, profiles/r01/guess128): time cuts at N <= 64,
@@ -1568,7 +1382,7 @@ struct hge_engine {
                 coop_epoch, nev, guess};
     void* sargs[] = {&t, &FDT, &olen, &len, &cs, &err};
     prof_begin("k_rounds_coop_spec");
-    HIPCHK(launch_resident(coop_spec_fn(), dim3(nw * N), dim3(coop_spec_bs), sargs));
+    HGE_HIPCHK(launch_resident(coop_spec_fn(), dim3(nw * N), dim3(coop_spec_bs), sargs));
     prof_end();
     int32_t* resume = s_cn.p + 2 * nw;
     KLAUNCH(k_coop_join, dim3(64), dim3(256), 0, st, t, cs, d_ssc.p, s.rstate, resume);
@@ -1623,12 +1437,12 @@ struct hge_engine {
                        &nostart, &nohist, &hmax, &nostart, &extra, &stall_ep, &force_exact, &mflag_ep, &paths,
                        &paths_next};
       prof_begin("k_rounds_direct");
-      HIPCHK(launch_resident(direct_fn(), dim3(N), dim3(1024), dargs));
+      HGE_HIPCHK(launch_resident(direct_fn(), dim3(N), dim3(1024), dargs));
       prof_end();
     } else {
       void* args[] = {&t, &FDT, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &dbg};
       prof_begin("k_rounds_coop");
-      HIPCHK(launch_resident((const void*)k_rounds_coop, dim3(N), dim3(COOP_BS), args));
+      HGE_HIPCHK(launch_resident((const void*)k_rounds_coop, dim3(N), dim3(COOP_BS), args));
       prof_end();
     }
     if (getenv("HGE_TEST_HANDOFF_FAIL")) {  // tests: the walk reports a hand-off timeout
@@ -1652,7 +1466,7 @@ struct hge_engine {
   unsigned long long* walk_paths() {
     if (!s_wpaths.p) {
       s_wpaths.need(4);
-      HIPCHK(hipMemset(s_wpaths.p, 0, 4 * sizeof(unsigned long long)));
+      HGE_HIPCHK(hipMemsetAsync(s_wpaths.p, 0, 4 * sizeof(unsigned long long), st));
     }
     walk_seq++;
     return s_wpaths.p + 2 * (walk_seq & 1);
@@ -1666,7 +1480,9 @@ struct hge_engine {
   SortCtl sort_ctl() {
     if (!s_spaths.p) {
       s_spaths.need(8);
-      HIPCHK(hipMemset(s_spaths.p, 0, 8 * sizeof(unsigned long long)));
+      // on the engine's stream (it does not wait for the null stream): cleared before the
+      // first stage deals buckets from the counter
+      HGE_HIPCHK(hipMemsetAsync(s_spaths.p, 0, 8 * sizeof(unsigned long long), st));
     }
     sort_seq++;
     sort_counted = true;
@@ -1706,12 +1522,14 @@ struct hge_engine {
     auto test_stop = [&](int stage) {  // HGE_TEST_W32_FAIL=stage: one failure after that stage
       if (test_w32_fail == stage) {
         test_w32_fail = 0;
-        throw EngineError(HGE_ERR_DEVICE, "test: to_wide32 stopped after stage " + std::to_string(stage));
+        throw Error(HGE_ERR_DEVICE, "test: to_wide32 stopped after stage " + std::to_string(stage));
       }
     };
     ensure_fdtd();  // (the pass reads the uint16 runs)
     if (!(w32_done & 4)) {
-      grow_chain_table(d_LA, ccap, false);
+      const size_t n = (size_t)N * ccap * N;  // [N][ccap][N], written by k_la16_to_la32 below
+      d_LA.regrow_rows(0, 0, 0, sizeof(int32_t) * n, n, false, st);
+      sync();
       w32_done |= 4;
       test_stop(1);
     }
@@ -1720,14 +1538,12 @@ struct hge_engine {
       for (int which = 0; which < 2; which++) {
         if (w32_done & (1 << which)) continue;
         DBuf<int32_t>& b = which ? d_FD : d_FDT;
-        int32_t* q = nullptr;
-        HIPCHK(hipMalloc(&q, sizeof(int32_t) * n));
+        DBuf<int32_t> q;
+        q.need(n);
         KLAUNCH(k_fdt16_to32, dim3((unsigned)std::min<size_t>(div_up(n, 256), 65536)), dim3(256), 0, st,
-                (const uint16_t*)b.p, q, n, which);
+                (const uint16_t*)b.p, q.p, n, which);
         sync();
-        b.free_();
-        b.p = q;
-        b.n = n;
+        b.adopt(std::move(q));
         w32_done |= 1 << which;
         test_stop(2 + which);
       }
@@ -1757,7 +1573,7 @@ struct hge_engine {
     const int Rprev = R, NB = 32;
     s_w32a.need(NB);
     for (int r = rlo;;) {
-      HIPCHK(hipMemsetAsync(s_w32a.p, 0, 4 * NB, st));
+      HGE_HIPCHK(hipMemsetAsync(s_w32a.p, 0, 4 * NB, st));
       int k = 0;
       for (; k < NB && r + k + 1 < Rcap; k++)
         KLAUNCH(k_round_step32, dim3(N), dim3(256), 0, st, t, (const int32_t*)s.olen, (const int32_t*)s.len,
@@ -1827,7 +1643,7 @@ struct hge_engine {
     int p = 0;
     for (int group = G == 1 ? 1 : 3;; group = 2) {
       for (int g = 0; g < group; g++, p++) {
-        if (p >= MAXP) throw EngineError(HGE_ERR_INTERNAL, "lastAncestors windows did not converge");
+        if (p >= MAXP) throw Error(HGE_ERR_INTERNAL, "lastAncestors windows did not converge");
         const int32_t* prev = p > 0 ? s_chg.p + p - 1 : nullptr;
         const int pass = p + 1;
 #define LWIN(NP)                                                                                         \
@@ -1914,7 +1730,7 @@ struct hge_engine {
     int sw = 0;
     for (int group = 12;; group = 8) {
       for (int g = 0; g < group; g++, sw++) {
-        if (sw >= MAXSW) throw EngineError(HGE_ERR_INTERNAL, "lastAncestors sweeps did not converge");
+        if (sw >= MAXSW) throw Error(HGE_ERR_INTERNAL, "lastAncestors sweeps did not converge");
         const int32_t* prev = sw > 0 ? s_chg.p + sw - 1 : nullptr;
         if (p16) {
           switch (NPt) {
@@ -1965,8 +1781,8 @@ struct hge_engine {
   // every reader of d_FDTD / d_FDTW: the whole table, when a bulk replay left it stale
   void ensure_fdtd() {
     if (!fdtd_stale) return;
-    if (!fdt16()) throw EngineError(HGE_ERR_INTERNAL, "stale FD timestamp rows past the uint16 runs");
-    HIPCHK(hipMemsetAsync(s_fdlo.p, 0, 4 * (size_t)N, st));
+    if (!fdt16()) throw Error(HGE_ERR_INTERNAL, "stale FD timestamp rows past the uint16 runs");
+    HGE_HIPCHK(hipMemsetAsync(s_fdlo.p, 0, 4 * (size_t)N, st));
     fdtd_pass("fdtd_ensure (k_fd_transpose_ts<uint16_t>)", div_up(std::max(fdtd_maxlen, 1), 64));
     fdtd_stale = false;
   }
@@ -2120,7 +1936,7 @@ struct hge_engine {
       launch_pending_fame(b);
       if (!b.hdr_done) out_init(b);
     }
-    if (b.fame_pending) throw EngineError(HGE_ERR_INTERNAL, "DecideFame's launch left pending");
+    if (b.fame_pending) throw Error(HGE_ERR_INTERNAL, "DecideFame's launch left pending");
     persist_fame(b);
     if (b.spl && b.got_order) {  // the parts' ordered slices, joined in call order
       split_commit(s_out.p, out_counts(), out_ids(b), b.out.ntxb, out_tx(b), order_out, counts_out);
@@ -2439,7 +2255,7 @@ struct hge_engine {
       // it (one launch in place of a memset and a copy)
       if (!b.hdr_done) out_init(b);
       s_recv.need(ncand);
-      HIPCHK(hipMemsetAsync(s_recv.p, 0xFF, 4 * ncand, st));
+      HGE_HIPCHK(hipMemsetAsync(s_recv.p, 0xFF, 4 * ncand, st));
       return;
     }
     SegInfo& si = b.si;
@@ -2550,7 +2366,7 @@ struct hge_engine {
     if (b.spl) {  // keep what this part's calls receive (k_split_filter)
       const int p = sp.part;
       const int32_t guard = p + 1 < sp.nparts ? (int32_t)sp.clo[p + 1] : INT32_MIN;
-      HIPCHK(hipMemsetAsync(s_small.p + 8, 0, 4, st));
+      HGE_HIPCHK(hipMemsetAsync(s_small.p + 8, 0, 4, st));
       KLAUNCH(k_split_filter, dim3(div_up(ncand, 256)), dim3(256), 0, st, (const int32_t*)cand, ncand,
               s_recv.p, sp.cb[p], sp.cb[p + 1] - 1, guard, s_small.p + 8);
     }
@@ -2693,15 +2509,15 @@ struct hge_engine {
     const size_t off = d2h_pinned(s_out.p, 4 * (b.got_order && !lazy ? b.out.total() : b.out.header()));
     const size_t off_tx = lazy ? d2h_pinned(s_out.p + b.out.o_tx, 4 * 2 * (size_t)b.out.ntxb) : 0;
     sync();
-    const int32_t* ho = (const int32_t*)(pin + off);
-    const int32_t* htx = !b.got_order ? nullptr : lazy ? (const int32_t*)(pin + off_tx) : ho + b.out.o_tx;
+    const int32_t* ho = (const int32_t*)(pin.p + off);
+    const int32_t* htx = !b.got_order ? nullptr : lazy ? (const int32_t*)(pin.p + off_tx) : ho + b.out.o_tx;
     const hge_plan::Results r = hge_plan::parse_results(b.out, ho, htx);
     if (b.got_order) {
       if (lazy) {  // delivered into the pinned order buffer (sized at hge_replay_prepare)
-        if ((size_t)r.nrecv > pin_ord_cap) throw EngineError(HGE_ERR_INTERNAL, "order buffer below the ordered count");
+        if ((size_t)r.nrecv > pin_ord.n) throw Error(HGE_ERR_INTERNAL, "order buffer below the ordered count");
         const int64_t td = now_ns();
         if (!b.wrote_direct && r.nrecv) {
-          HIPCHK(hipMemcpyAsync(pin_ord, out_ids(b), 4 * (size_t)r.nrecv, hipMemcpyDeviceToHost, st));
+          HGE_HIPCHK(hipMemcpyAsync(pin_ord.p, out_ids(b), 4 * (size_t)r.nrecv, hipMemcpyDeviceToHost, st));
           sync();
         }
         // the delivery's wall time after the sorts (hge_stage_times [5]; ~0 when written direct)
@@ -2735,7 +2551,7 @@ struct hge_engine {
     uint8_t* buf = (uint8_t*)x_buf(bytes);
     const int p = sp.part;
     if (P1[p] > P0[p])
-      HIPCHK(hipMemcpyAsync(buf + (size_t)p * bytes, s_dec.p + (size_t)P0[p] * N, (size_t)(P1[p] - P0[p]) * N,
+      HGE_HIPCHK(hipMemcpyAsync(buf + (size_t)p * bytes, s_dec.p + (size_t)P0[p] * N, (size_t)(P1[p] - P0[p]) * N,
                             hipMemcpyDeviceToDevice, st));
     x_gather(bytes, buf);
     if (emulating()) {  // the other parts' decisions of this fame iteration, from the record
@@ -2745,7 +2561,7 @@ struct hge_engine {
     }
     for (int g = 0; g < G; g++)
       if (g != p && P1[g] > P0[g])
-        HIPCHK(hipMemcpyAsync(s_dec.p + (size_t)P0[g] * N, buf + (size_t)g * bytes, (size_t)(P1[g] - P0[g]) * N,
+        HGE_HIPCHK(hipMemcpyAsync(s_dec.p + (size_t)P0[g] * N, buf + (size_t)g * bytes, (size_t)(P1[g] - P0[g]) * N,
                               hipMemcpyDeviceToDevice, st));
   }
 
@@ -2811,7 +2627,7 @@ struct hge_engine {
       off[g + 1] = off[g] + h0[0];
       ntx += (unsigned long long)(uint32_t)h0[4] | ((unsigned long long)(uint32_t)h0[5] << 32);
     }
-    if (bad) throw EngineError(HGE_ERR_SPLIT, "split replay: an event is received outside every part's range");
+    if (bad) throw Error(HGE_ERR_SPLIT, "split replay: an event is received outside every part's range");
     const int64_t tot = off[G];
     s_sord.need((size_t)std::max<int64_t>(tot, 1));
     s_soff.need((size_t)G + 1);
@@ -2821,11 +2637,11 @@ struct hge_engine {
     // the undetermined list: the last part's left candidates
     const int nleft = hd[(size_t)(G - 1) * L.ids + 1];
     if (nleft > 0)
-      HIPCHK(hipMemcpyAsync(d_und.p, buf + (size_t)(G - 1) * L.words + L.left, 4 * (size_t)nleft,
+      HGE_HIPCHK(hipMemcpyAsync(d_und.p, buf + (size_t)(G - 1) * L.words + L.left, 4 * (size_t)nleft,
                             hipMemcpyDeviceToDevice, st));
     const size_t po = d2h_pinned(s_sord.p, 4 * (size_t)tot);
     sync();
-    const int32_t* ids = (const int32_t*)(pin + po);
+    const int32_t* ids = (const int32_t*)(pin.p + po);
     consensus.insert(consensus.end(), ids, ids + tot);
     if (order_out) order_out->insert(order_out->end(), ids, ids + tot);
     ctx += (int64_t)ntx;
@@ -2910,7 +2726,7 @@ struct hge_engine {
       ensure_fdtd();
       return;
     }
-    HIPCHK(hipMemcpyAsync(s_fdlo.p, s_fdlo.p + N, 4 * (size_t)N, hipMemcpyDeviceToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(s_fdlo.p, s_fdlo.p + N, 4 * (size_t)N, hipMemcpyDeviceToDevice, st));
     KLAUNCH(k_und_low, dim3(std::max(1, std::min(div_up(b.ncand, 256), 1024))), dim3(256), 0, st,
             (const int32_t*)d_creator.p, (const int32_t*)d_index.p, (const int32_t*)d_und.p,
             (const int32_t*)out_word(hge_plan::ResultsLayout::kUndetermined), s_fdlo.p);
@@ -2998,10 +2814,10 @@ struct hge_engine {
     und_appended = false;
     if (!coords_a()) {
       dividing = false;
-      throw EngineError(HGE_ERR_INTERNAL, "online call: no coordinates to compute");
+      throw Error(HGE_ERR_INTERNAL, "online call: no coordinates to compute");
     }
     if (!cstep || !cstep->frontier_started)
-      throw EngineError(HGE_ERR_INTERNAL, "online call: frontier start not fused");
+      throw Error(HGE_ERR_INTERNAL, "online call: frontier start not fused");
     CoordStep s = *cstep;
     cstep.reset();
     // (n_divided == n0 and at most 65,536 candidates: the walk's block appends the new
@@ -3064,18 +2880,18 @@ struct hge_engine {
     const size_t off = d2h_pinned(s_out.p, 4 * b.out.total());
     const size_t offw = d2h_pinned(d_minw.p, 4 * ((size_t)Rcap + hge_plan::kTailPartial));
     sync();
-    const int32_t* hw = (const int32_t*)(pin + offw);
+    const int32_t* hw = (const int32_t*)(pin.p + offw);
     const hge_plan::RoundsTail rt = hge_plan::parse_rounds_tail(hw + Rcap, 0);
     if (rt.overflow) {  // (unreachable: ensure_rcap covers R + m + 4) the host state has moved on: refuse later calls
       failed = "online call: rounds table overflow past its bound";
-      throw EngineError(HGE_ERR_INTERNAL, failed);
+      throw Error(HGE_ERR_INTERNAL, failed);
     }
     R = rt.R;
     h_minw.assign(hw, hw + R);
     minw_full = false;
     mnr_key[0] = -1;
     update_rdiv();
-    const int32_t* ho = (const int32_t*)(pin + off);
+    const int32_t* ho = (const int32_t*)(pin.p + off);
     const hge_plan::Results r = hge_plan::parse_results(b.out, ho, ho + b.out.o_tx);
     commit_order(r, 1, true, &order, nullptr);
     if (r.lcr > lcr) commit_lcr(r.lcr, r.lcr_events);
@@ -3102,10 +2918,10 @@ struct hge_engine {
 // ---------------------------------------------------------------------------
 #define GUARD_BEGIN try {
 #define REFUSE_IF_FAILED(h) \
-  if (!(h)->failed.empty()) throw EngineError(HGE_ERR_INTERNAL, "engine state inconsistent since: " + (h)->failed);
+  if (!(h)->failed.empty()) throw Error(HGE_ERR_INTERNAL, "engine state inconsistent since: " + (h)->failed);
 #define GUARD_END(h)                 \
   }                                  \
-  catch (EngineError & e) {          \
+  catch (Error & e) {                \
     (h)->err = e.msg;                \
     return e.code;                   \
   }                                  \
@@ -3123,9 +2939,8 @@ int hge_create(int32_t n_participants, int64_t capacity_events, int32_t device, 
   hge_engine* h = new hge_engine();
   try {
     h->init(n_participants, capacity_events, device);
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     fprintf(stderr, "hge_create: %s\n", e.msg.c_str());
-    h->destroy();
     delete h;
     *out = nullptr;
     return e.code;
@@ -3135,8 +2950,6 @@ int hge_create(int32_t n_participants, int64_t capacity_events, int32_t device, 
 }
 
 void hge_destroy(hge_engine* h) {
-  if (!h) return;
-  h->destroy();
   delete h;
 }
 
@@ -3264,7 +3077,7 @@ int hge_replay_prepare(hge_engine* h, const hge_event* ev, int64_t n_sub,
   h->upload();
   h->cons_pin_n = 0;
   h->ensure_pin_ord((size_t)h->n_events);  // the replay's order is delivered here
-  HIPCHK(hipStreamSynchronize(h->st));
+  HGE_HIPCHK(hipStreamSynchronize(h->st));
   return HGE_OK;
   GUARD_END(h)
 }
@@ -3287,14 +3100,14 @@ static void replay_begin(hge_engine* h) {
   h->ext_on = false;
   h->w_start = std::chrono::steady_clock::now();
   h->reset_rounds();
-  HIPCHK(hipEventRecord(h->ev[0], h->st));
+  HGE_HIPCHK(hipEventRecord(h->ev[0], h->st));
   h->coords_a();
 }
 
 static void replay_end(hge_engine* h, int64_t* n_ordered) {
   const int64_t keep = h->n_events;
   if (h->cstep) h->coords_b();
-  HIPCHK(hipEventRecord(h->ev[1], h->st));
+  HGE_HIPCHK(hipEventRecord(h->ev[1], h->st));
   const auto w1 = std::chrono::steady_clock::now();
   h->n_divided = keep;
   h->update_rdiv();
@@ -3304,7 +3117,7 @@ static void replay_end(hge_engine* h, int64_t* n_ordered) {
   h->replay_counts.clear();
   // the consensus log (cleared above) is the replay's order, delivered to the pinned
   // order buffer in one copy (not staged through the arena into the log's vector)
-  h->lazy_order = h->pin_ord_cap >= (size_t)keep;
+  h->lazy_order = h->pin_ord.n >= (size_t)keep;
   try {
     h->consensus_batch(h->replay_calls, true, true, true, nullptr, &h->replay_counts);
   } catch (...) {
@@ -3312,12 +3125,12 @@ static void replay_end(hge_engine* h, int64_t* n_ordered) {
     throw;
   }
   h->lazy_order = false;
-  HIPCHK(hipEventRecord(h->ev[2], h->st));
-  HIPCHK(hipEventSynchronize(h->ev[2]));
+  HGE_HIPCHK(hipEventRecord(h->ev[2], h->st));
+  HGE_HIPCHK(hipEventSynchronize(h->ev[2]));
   const auto w2 = std::chrono::steady_clock::now();
   float a = 0, b = 0;
-  HIPCHK(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-  HIPCHK(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+  HGE_HIPCHK(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+  HGE_HIPCHK(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
   auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
     return (float)std::chrono::duration<double, std::milli>(y - x).count();
   };
@@ -3491,11 +3304,11 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
     h->h2d(cut, stopcut, 4 * (size_t)N);
   }
   int32_t* rstate = h->s_hstate.p + N;
-  HIPCHK(hipMemsetAsync(rstate, 0, 16, h->st));
+  HGE_HIPCHK(hipMemsetAsync(rstate, 0, 16, h->st));
   h->s_bar.need(2);
   h->s_gran.need(2 * (size_t)N);
-  HIPCHK(hipMemsetAsync(h->s_bar.p, 0, 8, h->st));
-  HIPCHK(hipMemsetAsync(h->s_gran.p, 0, 16 * (size_t)N, h->st));
+  HGE_HIPCHK(hipMemsetAsync(h->s_bar.p, 0, 8, h->st));
+  HGE_HIPCHK(hipMemsetAsync(h->s_gran.p, 0, 16 * (size_t)N, h->st));
   auto lk = h->frontier_lock();  // until the walk has drained (the sync below)
   Tables t = h->tables();
   const int32_t* olen = h->cstep->olen;
@@ -3516,13 +3329,13 @@ int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcu
   void* args[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
                   &st0, &hist, &hm, &cut, &ex, &nostall, &force_exact, &nomflag, &paths, &paths_next};
   h->prof_begin("k_rounds_direct_walk");
-  HIPCHK(h->launch_resident(h->direct_fn(), dim3(N), dim3(1024), args));
+  HGE_HIPCHK(h->launch_resident(h->direct_fn(), dim3(N), dim3(1024), args));
   h->prof_end();
   int32_t rs[2] = {0, 0}, e = 0;
   h->d2h(rs, rstate, 8);
   h->d2h(&e, err, 4);
   h->sync();
-  if (e) throw EngineError(HGE_ERR_DEVICE, "rounds frontier hand-off timed out");
+  if (e) throw Error(HGE_ERR_DEVICE, "rounds frontier hand-off timed out");
   const int n = std::max(1, std::min(rs[0], hmax));
   if (rows_out) h->readback(rows_out, h->s_hist.p, (size_t)n * N);
   if (ssc_out) h->readback(ssc_out, h->s_hssc.p, (size_t)n * N * NW);
@@ -3572,9 +3385,9 @@ int hge_replay_fetch(hge_engine* h, int32_t* order_out, int64_t cap, int64_t* ca
     for (int k = 1; k < nt; k++)
       th.emplace_back([=] {
         const int64_t lo = b * k / nt, hi = b * (k + 1) / nt;
-        memcpy(order_out + a + lo, h->pin_ord + lo, 4 * (size_t)(hi - lo));
+        memcpy(order_out + a + lo, h->pin_ord.p + lo, 4 * (size_t)(hi - lo));
       });
-    if (b > 0) memcpy(order_out + a, h->pin_ord, 4 * (size_t)(b / nt));
+    if (b > 0) memcpy(order_out + a, h->pin_ord.p, 4 * (size_t)(b / nt));
     for (auto& x : th) x.join();
   }
   if (call_counts_out)
@@ -3588,7 +3401,7 @@ int hge_replay_order(hge_engine* h, const int32_t** ids, int64_t* n) {
   GUARD_BEGIN
   if (!h->consensus.empty() || !h->cons_pin_n) h->consensus_sync();  // the whole log in one place
   if (h->cons_pin_n) {
-    *ids = h->pin_ord;
+    *ids = h->pin_ord.p;
     *n = h->cons_pin_n;
   } else {
     *ids = h->consensus.data();
@@ -3625,7 +3438,7 @@ static int64_t window_len(int64_t tot, int64_t size) {
 int64_t hge_consensus_events(hge_engine* h, int32_t* ids_out, int64_t cap) {
   try {
     h->consensus_sync();
-  } catch (const EngineError& e) {
+  } catch (const Error& e) {
     h->err = e.msg;
     return -1;
   }
@@ -3636,7 +3449,7 @@ int64_t hge_consensus_events(hge_engine* h, int32_t* ids_out, int64_t cap) {
 int64_t hge_consensus_log(hge_engine* h, int64_t from, int32_t* ids_out, int64_t cap) {
   try {
     h->consensus_sync();
-  } catch (const EngineError& e) {
+  } catch (const Error& e) {
     h->err = e.msg;
     return -1;
   }
@@ -3651,7 +3464,7 @@ int64_t hge_undetermined(hge_engine* h, int32_t* ids_out, int64_t cap) {
       int64_t m = std::min<int64_t>(cap, h->n_und);
       h->readback(ids_out, h->d_und.p, m);
     }
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3673,7 +3486,7 @@ int32_t hge_round_of(hge_engine* h, int32_t id) {
     if (id < 0 || id >= h->n_events) return -1;
     h->coords();
     return read1(h, h->d_round.p + id);
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3685,7 +3498,7 @@ int32_t hge_is_witness(hge_engine* h, int32_t id) {
     uint8_t v = 0;
     h->readback(&v, h->d_wit.p + id, 1);
     return v;
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3696,7 +3509,7 @@ int32_t hge_round_witness(hge_engine* h, int32_t round, int32_t creator) {
     int32_t w = read1(h, h->d_W.p + (size_t)round * h->N + creator);
     if (w >= h->n_divided) return -1;
     return w;
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3707,7 +3520,7 @@ int32_t hge_fame(hge_engine* h, int32_t round, int32_t creator) {
     uint8_t v = 0;
     h->readback(&v, h->d_fame.p + (size_t)round * h->N + creator, 1);
     return v;
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3716,7 +3529,7 @@ int32_t hge_round_events(hge_engine* h, int32_t round) {
   try {
     if (round < 0 || round >= h->R) return 0;
     return read1(h, h->d_rcnt.p + round);
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3757,7 +3570,7 @@ int32_t hge_round_received(hge_engine* h, int32_t id) {
   try {
     if (id < 0 || id >= h->n_events) return -1;
     return read1(h, h->d_rr.p + id);
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3768,7 +3581,7 @@ int64_t hge_consensus_timestamp(hge_engine* h, int32_t id) {
     int64_t v = 0;
     h->readback(&v, h->d_cts.p + id, 1);
     return v;
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return e.code;
   }
@@ -3832,7 +3645,7 @@ int32_t hge_oldest_self_ancestor_to_see(hge_engine* h, int32_t x, int32_t y) {
   if (a <= h->h_index[x]) {
     try {
       return read1(h, h->d_chain.p + (size_t)cx * h->ccap + a);
-    } catch (EngineError& e) {
+    } catch (Error& e) {
       h->err = e.msg;
       return -1;
     }
@@ -3960,14 +3773,14 @@ int hge_consensus_timestamp_sources(hge_engine* h, const int32_t* ids, int64_t n
   GUARD_BEGIN
   if (n == 0) return HGE_OK;
   for (int64_t i = 0; i < n; i++)
-    if (ids[i] < 0 || ids[i] >= h->n_events) throw EngineError(HGE_ERR_ARG, "hge_consensus_timestamp_sources: unknown id");
+    if (ids[i] < 0 || ids[i] >= h->n_events) throw Error(HGE_ERR_ARG, "hge_consensus_timestamp_sources: unknown id");
   h->s_src.need((size_t)n * 2);
   h->h2d(h->s_src.p, ids, 4 * (size_t)n);
   hipLaunchKernelGGL(k_cts_source, dim3((unsigned)div_up(n, 4)), dim3(256), 0, h->st, h->tables(),
                      (const int32_t*)h->s_src.p, (int)n, (const int32_t*)h->d_rr.p, (const int64_t*)h->d_cts.p,
                      h->s_src.p + n);
   const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) throw EngineError(HGE_ERR_DEVICE, std::string("launch k_cts_source: ") + hipGetErrorString(le));
+  if (le != hipSuccess) throw Error(HGE_ERR_DEVICE, std::string("launch k_cts_source: ") + hipGetErrorString(le));
   h->readback(src_out, h->s_src.p + n, (size_t)n);
   return HGE_OK;
   GUARD_END(h)
@@ -4013,7 +3826,7 @@ int32_t hge_round_inc(hge_engine* h, int32_t x) {
     for (int i = 0; i < h->N; i++)
       if (w[i] >= 0 && w[i] < h->n_events) c += hge_strongly_see(h, x, w[i]);
     return c >= h->SM ? 1 : 0;
-  } catch (EngineError& e) {
+  } catch (Error& e) {
     h->err = e.msg;
     return 0;
   }

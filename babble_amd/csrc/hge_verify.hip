@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/hge.h"
+#include "hge_hip.h"
 #include "hge_p256.h"
 
 namespace {
@@ -75,31 +76,8 @@ __global__ __launch_bounds__(kVerifyThreads) void k_ecdsa_p256_verify(
   ok[i] = v;
 }
 
-struct VerifyError {
-  int code;
-};
-#define VCHK(x)                                            \
-  do {                                                     \
-    if ((x) != hipSuccess) throw VerifyError{HGE_ERR_DEVICE}; \
-  } while (0)
-
-template <typename T>
-struct DBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  void need(size_t n) {
-    n = std::max<size_t>(n, 1);
-    if (n <= cap) return;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) throw VerifyError{HGE_ERR_DEVICE};
-    cap = n;
-  }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
+using hge::DBuf;
+using hge::Error;
 
 // G's window table, once per process, by the code the device runs for the keys
 const affine* generator_table() {
@@ -114,15 +92,12 @@ class Verifier {
  public:
   explicit Verifier(int device) {
     if (hipGetDevice(&prev_) != hipSuccess) prev_ = -1;
-    VCHK(hipSetDevice(device));
-    VCHK(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
-    VCHK(hipEventCreate(&e0_));
-    VCHK(hipEventCreate(&e1_));
+    HGE_HIPCHK(hipSetDevice(device));
+    s_.create();
+    e0_.create();
+    e1_.create();
   }
   ~Verifier() {
-    if (e0_) (void)hipEventDestroy(e0_);
-    if (e1_) (void)hipEventDestroy(e1_);
-    if (s_) (void)hipStreamDestroy(s_);
     if (prev_ >= 0) (void)hipSetDevice(prev_);
   }
   double device_ms() const { return ms_; }
@@ -132,13 +107,13 @@ class Verifier {
     tabs_.need((size_t)kTableEntries * n_keys);
     valid_.need(n_keys);
     gtab_.need(kTableEntries);
-    VCHK(hipMemcpyAsync(keys_.p, keys, 65 * (size_t)n_keys, hipMemcpyHostToDevice, s_));
-    VCHK(hipMemcpyAsync(gtab_.p, generator_table(), sizeof(affine) * kTableEntries, hipMemcpyHostToDevice, s_));
-    VCHK(hipEventRecord(e0_, s_));
+    HGE_HIPCHK(hipMemcpyAsync(keys_.p, keys, 65 * (size_t)n_keys, hipMemcpyHostToDevice, s_));
+    HGE_HIPCHK(hipMemcpyAsync(gtab_.p, generator_table(), sizeof(affine) * kTableEntries, hipMemcpyHostToDevice, s_));
+    HGE_HIPCHK(hipEventRecord(e0_, s_));
     k_p256_key_tables<<<(n_keys + kVerifyThreads - 1) / kVerifyThreads, kVerifyThreads, 0, s_>>>(n_keys, keys_.p,
                                                                                                 tabs_.p, valid_.p);
-    VCHK(hipGetLastError());
-    VCHK(hipEventRecord(e1_, s_));
+    HGE_HIPCHK(hipGetLastError());
+    HGE_HIPCHK(hipEventRecord(e1_, s_));
     finish();
   }
 
@@ -147,10 +122,10 @@ class Verifier {
     for (int64_t lo = 0; lo < n; lo += kChunkEvents) {
       const int64_t m = std::min(kChunkEvents, n - lo);
       upload_bodies(m, data, off + lo);
-      VCHK(hipEventRecord(e0_, s_));
+      HGE_HIPCHK(hipEventRecord(e0_, s_));
       launch_sha(m, off[lo]);
-      VCHK(hipEventRecord(e1_, s_));
-      VCHK(hipMemcpyAsync(out + 32 * lo, dig_.p, 32 * (size_t)m, hipMemcpyDeviceToHost, s_));
+      HGE_HIPCHK(hipEventRecord(e1_, s_));
+      HGE_HIPCHK(hipMemcpyAsync(out + 32 * lo, dig_.p, 32 * (size_t)m, hipMemcpyDeviceToHost, s_));
       finish();
     }
   }
@@ -160,12 +135,12 @@ class Verifier {
     for (int64_t lo = 0; lo < n; lo += kChunkEvents) {
       const int64_t m = std::min(kChunkEvents, n - lo);
       dig_.need(32 * (size_t)m);
-      VCHK(hipMemcpyAsync(dig_.p, digests + 32 * lo, 32 * (size_t)m, hipMemcpyHostToDevice, s_));
+      HGE_HIPCHK(hipMemcpyAsync(dig_.p, digests + 32 * lo, 32 * (size_t)m, hipMemcpyHostToDevice, s_));
       upload_sigs(m, key_idx + lo, sigs + 64 * lo);
-      VCHK(hipEventRecord(e0_, s_));
+      HGE_HIPCHK(hipEventRecord(e0_, s_));
       launch_verify(m);
-      VCHK(hipEventRecord(e1_, s_));
-      VCHK(hipMemcpyAsync(ok_out + lo, ok_.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s_));
+      HGE_HIPCHK(hipEventRecord(e1_, s_));
+      HGE_HIPCHK(hipMemcpyAsync(ok_out + lo, ok_.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s_));
       finish();
     }
   }
@@ -176,12 +151,12 @@ class Verifier {
       const int64_t m = std::min(kChunkEvents, n - lo);
       upload_bodies(m, bodies, off + lo);
       upload_sigs(m, key_idx + lo, sigs + 64 * lo);
-      VCHK(hipEventRecord(e0_, s_));
+      HGE_HIPCHK(hipEventRecord(e0_, s_));
       launch_sha(m, off[lo]);
       launch_verify(m);
-      VCHK(hipEventRecord(e1_, s_));
-      if (hash_out) VCHK(hipMemcpyAsync(hash_out + 32 * lo, dig_.p, 32 * (size_t)m, hipMemcpyDeviceToHost, s_));
-      VCHK(hipMemcpyAsync(ok_out + lo, ok_.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s_));
+      HGE_HIPCHK(hipEventRecord(e1_, s_));
+      if (hash_out) HGE_HIPCHK(hipMemcpyAsync(hash_out + 32 * lo, dig_.p, 32 * (size_t)m, hipMemcpyDeviceToHost, s_));
+      HGE_HIPCHK(hipMemcpyAsync(ok_out + lo, ok_.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s_));
       finish();
     }
   }
@@ -193,37 +168,37 @@ class Verifier {
     data_.need(bytes);
     off_.need((size_t)m + 1);
     dig_.need(32 * (size_t)m);
-    if (bytes) VCHK(hipMemcpyAsync(data_.p, data + off[0], bytes, hipMemcpyHostToDevice, s_));
-    VCHK(hipMemcpyAsync(off_.p, off, sizeof(int64_t) * ((size_t)m + 1), hipMemcpyHostToDevice, s_));
+    if (bytes) HGE_HIPCHK(hipMemcpyAsync(data_.p, data + off[0], bytes, hipMemcpyHostToDevice, s_));
+    HGE_HIPCHK(hipMemcpyAsync(off_.p, off, sizeof(int64_t) * ((size_t)m + 1), hipMemcpyHostToDevice, s_));
   }
   void upload_sigs(int64_t m, const int32_t* key_idx, const uint8_t* sigs) {
     kidx_.need(m);
     sigs_.need(64 * (size_t)m);
     ok_.need(m);
-    VCHK(hipMemcpyAsync(kidx_.p, key_idx, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, s_));
-    VCHK(hipMemcpyAsync(sigs_.p, sigs, 64 * (size_t)m, hipMemcpyHostToDevice, s_));
+    HGE_HIPCHK(hipMemcpyAsync(kidx_.p, key_idx, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, s_));
+    HGE_HIPCHK(hipMemcpyAsync(sigs_.p, sigs, 64 * (size_t)m, hipMemcpyHostToDevice, s_));
   }
   void launch_sha(int64_t m, int64_t base) {
     k_sha256_bodies<<<(unsigned)((m + kShaThreads - 1) / kShaThreads), kShaThreads, 0, s_>>>(m, data_.p, off_.p, base,
                                                                                               dig_.p);
-    VCHK(hipGetLastError());
+    HGE_HIPCHK(hipGetLastError());
   }
   void launch_verify(int64_t m) {
     k_ecdsa_p256_verify<<<(unsigned)((m + kVerifyThreads - 1) / kVerifyThreads), kVerifyThreads, 0, s_>>>(
         m, dig_.p, kidx_.p, sigs_.p, gtab_.p, tabs_.p, valid_.p, ok_.p);
-    VCHK(hipGetLastError());
+    HGE_HIPCHK(hipGetLastError());
   }
   // wait for the chunk (the host buffers are the caller's: nothing may be in flight on return)
   void finish() {
-    VCHK(hipStreamSynchronize(s_));
+    HGE_HIPCHK(hipStreamSynchronize(s_));
     float ms = 0;
-    VCHK(hipEventElapsedTime(&ms, e0_, e1_));
+    HGE_HIPCHK(hipEventElapsedTime(&ms, e0_, e1_));
     ms_ += ms;
   }
 
   int prev_ = -1;
-  hipStream_t s_ = nullptr;
-  hipEvent_t e0_ = nullptr, e1_ = nullptr;
+  hge::Stream s_;  // before the buffers: destroyed after them
+  hge::Event e0_, e1_;
   double ms_ = 0;
   DBuf<uint8_t> keys_, data_, dig_, sigs_;
   DBuf<affine> tabs_, gtab_;
@@ -247,7 +222,7 @@ template <class F>
 int guarded(F&& f) {
   try {
     return f();
-  } catch (const VerifyError& e) {
+  } catch (const Error& e) {
     return e.code;
   } catch (const std::bad_alloc&) {
     return HGE_ERR_INTERNAL;
