@@ -27,6 +27,10 @@
 #include "../../include/hge.h"
 #include "hge_hip.h"
 #include "hge_plan.h"
+#include "hge_hostlog.h"
+#include "hge_hooks.h"
+#include "hge_launch.h"
+#include "hge_xfer.h"
 #include "hge_kernels.hip"
 #include "hge_median_rows.hip"
 #include "hge_wide32.hip"
@@ -38,49 +42,6 @@
 
 using namespace hge;
 
-// every launch is checked: a launch the runtime refuses (e.g. too much LDS)
-// must fail the call, never leave a table silently unwritten
-// KLAUNCH_AS: a kernel pointer chosen at run time (WalkKernels) under its instantiation's name
-#define KLAUNCH_AS(name, kern, ...)                                                    \
-  do {                                                                                 \
-    hp.launches++;                                                                     \
-    prof_begin(name);                                                                  \
-    hipLaunchKernelGGL(kern, __VA_ARGS__);                                             \
-    const hipError_t le_ = hipGetLastError();                                          \
-    if (le_ != hipSuccess)                                                             \
-      throw Error(HGE_ERR_DEVICE, std::string("launch ") + name + ": " + hipGetErrorString(le_)); \
-    prof_end();                                                                        \
-  } while (0)
-#define KLAUNCH(kern, ...) KLAUNCH_AS(#kern, kern, __VA_ARGS__)
-
-// Run-time NW (1..4) -> template argument, the one place that does it:
-//   KLAUNCH_NW(NW, SHAPE, kernel, [template arguments around the width,] launch arguments...)
-// SHAPE says where the width goes and whether the name is parenthesised, so that each
-// case hands KLAUNCH the kernel with the number in place and hge_kernel_stats keeps
-// reporting "k_median_wave<4>" and "(k_fame_call<64, 4, false>)" (bench.py reads them).
-// KLAUNCH_NW2: N > 64 only (no <1> instance of the kernel exists).
-#define NW_T(B, kern, ...) KLAUNCH(kern<B>, __VA_ARGS__)
-#define NW_PT(B, kern, ...) KLAUNCH((kern<B>), __VA_ARGS__)
-#define NW_PAT(B, kern, A, ...) KLAUNCH((kern<A, B>), __VA_ARGS__)
-#define NW_PATC(B, kern, A, C, ...) KLAUNCH((kern<A, B, C>), __VA_ARGS__)
-#define NW_SWITCH_(nw, CASE1, SHAPE, ...)                          \
-  switch (nw) {                                                    \
-    CASE1                                                          \
-    case 2:                                                        \
-      SHAPE(2, __VA_ARGS__);                                       \
-      break;                                                       \
-    case 3:                                                        \
-      SHAPE(3, __VA_ARGS__);                                       \
-      break;                                                       \
-    case 4:                                                        \
-      SHAPE(4, __VA_ARGS__);                                       \
-      break;                                                       \
-    default:                                                       \
-      throw Error(HGE_ERR_INTERNAL, "unsupported N");              \
-  }
-#define KLAUNCH_NW(nw, SHAPE, ...) NW_SWITCH_(nw, case 1 : SHAPE(1, __VA_ARGS__); break;, SHAPE, __VA_ARGS__)
-#define KLAUNCH_NW2(nw, SHAPE, ...) NW_SWITCH_(nw, , SHAPE, __VA_ARGS__)
-
 namespace {
 
 inline int div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
@@ -89,75 +50,115 @@ static const int32_t kInf = INF32;
 }  // namespace
 
 struct hge_engine {
+  // ==== State, grouped by lifetime (DESIGN.md §State and lifetimes) ====================
+  // Every data member is declared in this block, in the part whose reset it follows.
+  // Resetting a part is assigning a fresh one, so a new member needs nothing else.
+
+  // ---- what the parts hold: a pending coordinate step, a split plan ----
+  // coords_a (the control block, lastAncestors, firstDescendants) then coords_b (the
+  // rounds frontier and what follows).  What their stages share is a CoordStep: coords_a
+  // makes it, coords_b (or online_fast) takes it, and in between the step is pending
+  // (cons.cstep has a value): the cross-GPU split (hge_split_*) runs a walker there.
+  struct CoordStep {
+    bool fresh = false;      // nothing had coordinates or rounds before
+    int64_t n0 = 0, n1 = 0;  // the new ids
+    int maxnew = 0;          // most new positions on one chain, + 1
+    int tot0 = 0;            // a fresh walk's fss rows (every chain's length)
+    int SEG = 0, nseg = 0;   // the sweeps' segment length and count
+    int maxlen = 0, minlen = 0;  // the longest and the shortest chain
+    enum class La { Windows, Seq, Sweeps } la = La::Sweeps;  // how lastAncestors are computed
+    // the control block's regions in s_kctl (bind_kctl)
+    int32_t *rstate = nullptr, *olen = nullptr, *len = nullptr, *plo = nullptr, *qlo = nullptr;
+    int32_t *fss_lo = nullptr, *fss_off = nullptr, *fss_total = nullptr, *segbase = nullptr;
+    const int2* segs = nullptr;
+    int32_t *cand_lo = nullptr, *cand_hi = nullptr;  // a split part's candidates (else null)
+    int32_t* risky1 = nullptr;  // the one-window lastAncestors pass's risky id (-1 as uploaded)
+    const UpEv* up = nullptr;   // the chain-table fill's source: the packed upload, or null (the tables)
+    UpDst up_dst{};
+    // what earlier kernels of the step did already
+    bool frontier_started = false;  // k_frontier_start's block (k_chain_fill_qlo, k_la_seq)
+    bool qlo_done = false;          // k_fd_qlo's blocks (the same two)
+    bool fd_done = false;           // the FD rows and FDT runs (k_la_seq, N <= 16)
+    // the FD rows without their timestamp offsets (k_fd_rows16): a fresh bulk replay whose
+    // median reads the rows itself (k_median_rows)
+    bool fd_rows_only = false;
+    bool take_frontier_start() { return std::exchange(frontier_started, false); }  // (a later attempt starts again)
+  };
+  // One hashgraph sharded across GPUs by time (hge_split_plan, DESIGN.md §6): part
+  // p owns the events [a_p, a_{p+1}) and the calls [cb_p, cb_{p+1}).  Every part
+  // computes the coordinates and walks the rounds recurrence (sequential: it cannot
+  // be split exactly, DESIGN.md §6); part p then decides the fame of the rounds whose
+  // first witness it owns and commits the events its calls receive (candidates from
+  // cand_lo_p, the only FD timestamp rows it writes), and the parts exchange fame
+  // decisions and ordered slices through the caller's all-gather (hge_split_exchange).
+  struct SplitPlan {
+    int part = 0, nparts = 0;
+    std::vector<int64_t> a;     // event bounds, nparts + 1
+    std::vector<int32_t> cb;    // call bounds, nparts + 1
+    std::vector<int64_t> clo;   // first candidate of every part
+  };
+
+  // ---- engine lifetime: never reset ----
   int N = 0, NW = 1, SM = 1;
   int device = 0;
   // declared before every buffer and event, so destroyed after them
   Stream st;
   std::string err;
-
-  // ---- host control state ----
-  std::vector<int32_t> h_creator, h_index, h_sp, h_op, h_ntx;
-  std::vector<int64_t> h_ts;
-  std::vector<uint64_t> h_S;
-  std::vector<uint8_t> h_coin;
-  std::vector<int32_t> chain_len, chain_last;
-  int64_t n_events = 0;     // accepted (host)
-  int64_t n_dev = 0;        // uploaded
-  int64_t n_coords = 0;     // coordinates + rounds computed
-  int64_t n_divided = 0;    // visible to DecideFame / FindOrder (DivideRounds)
-  std::vector<int32_t> coords_len;  // chain lengths at n_coords
-  std::vector<int32_t> h_lens;      // staging for the chain-length upload
-
-  int R = 0;                // Store.Rounds()
-  int R_set = 0;            // rounds recorded by hge_set_round (Store.SetRound)
-  std::vector<std::vector<int32_t>> h_chain;  // participantEventsCache: ids per creator
+  HostPhases hp;
+  Xfer xfer{st, hp};    // the pinned staging arena (hge_xfer.h)
+  KernelProf prof{st};  // per-kernel HIP-event timing on the engine stream (hge_set_profiling)
   int64_t cache_size = 0;   // Store.CacheSize() for the rolling views (0 = unbounded)
-  int32_t chain_limit = INT32_MAX;  // longest chain of the uint16 wide path (then: to_wide32)
-  int32_t chain_limit0 = INT32_MAX;
-  // N > 32 past chain_limit: int32 positions for good (hge_wide32.hip); pending until
-  // the next coordinate step converts the packed table
-  bool wide32 = false, wide32_pending = false;
-  // to_wide32's progress bits: 1 the runs widened, 2 the FD rows, 4 the int32 LA table allocated
-  int w32_done = 0;
-  // what failed, when an internal failure left the host and device state apart (empty:
-  // none): every later consensus call refuses (HGE_ERR_INTERNAL) until a new stream
-  // (hge_replay_prepare)
-  std::string failed;
+  int32_t chain_limit0 = INT32_MAX;  // every stream's first chain limit (init)
+  // the caller's all-gather of a split replay (hge_split_exchange)
+  hge_exchange_fn x_fn = nullptr;
+  void* x_ctx = nullptr;
+  // measurement aid (hge_split_emulate): an unsplit replay records what every part
+  // of a split contributes to the exchanges (the fame decisions of every fame
+  // iteration, the order, per-call batches, round received / timestamps, the
+  // undetermined list); a split part run without an exchange then takes the other
+  // parts' slots from the record, so one GPU times each part of a G-way split alone.
+  // Kept on purpose: only hge_split_emulate starts a record or drops one, so it outlives
+  // the replays that use it; the caller records again after staging another stream.
+  bool rec_on = false, rec_have = false;
+  std::vector<std::vector<uint8_t>> rec_dec;
+  std::vector<int32_t> rec_order, rec_rr, rec_left;
+  std::vector<int64_t> rec_counts, rec_cts;
+  // hooks read at create (hge_hooks.h)
   // test hook (HGE_TEST_W32_FAIL=k): to_wide32 fails once after its stage k.  Stages count
   // in the order to_wide32 runs them, not by bit value: 1 the int32 LA table allocated
   // (bit 4), 2 the runs widened (bit 1), 3 the FD rows widened (bit 2)
-  int test_w32_fail = getenv("HGE_TEST_W32_FAIL") ? atoi(getenv("HGE_TEST_W32_FAIL")) : 0;
-  int lcr = -1;             // LastConsensusRound (-1 nil)
-  int lcre = 0;             // LastCommitedRoundEvents
-  int64_t ctx = 0;          // ConsensusTransactions
-  std::vector<int32_t> consensus;  // the consensus log (unbounded)
+  int test_w32_fail = hge_hooks::test_w32_fail();
+  // test hook (HGE_TEST_MEDIAN_ROWS_FALLBACK=1): the coordinate step skips the timestamps
+  // but the median takes k_median_wave, so ensure_fdtd()'s full pass runs
+  bool test_rows_fallback = hge_hooks::test_median_rows_fallback();
+  bool dbg_on = hge_hooks::stamps();
+  // launch geometry and residency, asked of the device once
+  int ncu_cache = 0;
+  int walk_chk[2] = {448, 2};        // checker threads, poll pause
+  bool coop_checked = false;
+  int coop_nb = 0, coop_ncu = 0, coop_spec_nb = -1, coop_spec_bs = 0;
+  std::vector<std::pair<std::pair<const void*, int>, int>> resident_nb;  // launch_resident's blocks per CU
+  bool frontier_fallback = false;  // k_round_step32 for good after a hand-off timeout
+  int64_t n_frontier_fallbacks = 0;
+  // These tag or address device memory that no reset clears (the walkers' epoch-tagged
+  // histories, the two-slot path counters), so they keep counting across streams.
+  uint32_t walk_epoch = 0, coop_epoch = 0;
+  int walk_seq = 0, sort_seq = 0;
+  bool sort_counted = false;  // the last order stage launched a counting kernel (hge_sort_paths)
+  // what the last step did, for the readers of hge_coordinate_sweeps and hge_stage_times
+  int n_sweeps = 0;
+  float stage_ms[7] = {};
+  Event ev[8];
+  // host staging of the control blocks and the sweeps' segments (rebuilt by every step)
+  std::vector<int32_t> h_cctl, h_kctl;
+  std::vector<hge_plan::Seg> h_segs;
   // A replay delivers its order to host memory inside hge_replay_run: one DMA copy from
   // the results block into a pinned buffer sized at hge_replay_prepare (pin_ord), the
-  // log's last cons_pin_n ids.  Readers take it from there (hge_replay_order: a view,
+  // log's last cons.cons_pin_n ids.  Readers take it from there (hge_replay_order: a view,
   // hge_replay_fetch: one copy); the log's vector gets them on first use
   // (consensus_sync), outside the replay.
   PBuf<int32_t> pin_ord;
   int32_t* pin_ord_dev = nullptr;  // its device-side address (the sorts write there)
-  int64_t cons_pin_n = 0;
-  bool lazy_order = false;
-  int64_t consensus_size() const { return (int64_t)consensus.size() + cons_pin_n; }
-  void consensus_sync() {
-    if (!cons_pin_n) return;
-    consensus.insert(consensus.end(), pin_ord.p, pin_ord.p + cons_pin_n);
-    cons_pin_n = 0;
-  }
-  void ensure_pin_ord(size_t n) {
-    if (n <= pin_ord.n && pin_ord.p) return;
-    consensus_sync();
-    pin_ord_dev = nullptr;
-    pin_ord.need(std::max<size_t>(n, 1));
-    pin_ord_dev = PinnedMem::device_ptr(pin_ord.p);
-  }
-  int64_t n_und = 0;
-
-  // replay staging
-  std::vector<int64_t> replay_calls;  // n_c per call (accepted counts)
-  std::vector<int64_t> replay_counts;
 
   // ---- device tables ----
   int64_t Ecap = 0;
@@ -167,14 +168,20 @@ struct hge_engine {
   DBuf<uint64_t> d_S;
   DBuf<uint8_t> d_coin, d_wit;
   DBuf<int32_t> d_chain, d_LA, d_FD, d_FSS;
-  DBuf<int32_t> s_w32, s_w32a;  // to_wide32 / rounds_step32 scratch
   DBuf<uint32_t> d_LA16;  // N > 32: the sweeps' packed (LA + 1) table (hge_coords.hip)
   DBuf<int2> d_opcp;  // [N][ccap] other-parent coordinates (k_chain_fill)
   DBuf<int64_t> d_tsch;  // [N][ccap] timestamps in chain layout (k_chain_fill)
   DBuf<int32_t> d_C, d_W, d_rcnt, d_minw;
   DBuf<uint64_t> d_ssb, d_seeb;
   DBuf<uint8_t> d_fame;
-  // scratch
+  DBuf<int32_t> d_FDT;   // FD in run layout [N][N][ccap] (persistent)
+  DBuf<int32_t> d_FDTD;  // N > 16: timestamp offsets at the FD positions (the wide median)
+  DBuf<uint8_t> d_FDTW;  // N > 16: per (row, 64-column tile) out-of-range flags of d_FDTD
+  DBuf<int32_t> d_WLA;   // N > 16: round frontier rows transposed (k_witness_la)
+  DBuf<uint16_t> d_WLR;  // N > 64, packed path: the same rows row-major as LA + 1 (theta)
+  DBuf<uint64_t> d_ssc;
+  // ---- scratch ----
+  DBuf<int32_t> s_w32, s_w32a;  // to_wide32 / rounds_step32 scratch
   DBuf<int32_t> s_small, s_newwit;
   DBuf<int32_t> s_LCR, s_clast;
   DBuf<uint8_t> s_dec, s_decbit;
@@ -182,80 +189,148 @@ struct hge_engine {
   DBuf<uint8_t> s_segdec;
   DBuf<uint64_t> s_segfws;
   DBuf<int32_t> s_recv, s_rr, s_fund, s_upos, s_und2, s_bpos, s_vis;
-  bool vis_all = false;  // this batch: one call seeing every event (no visibility table)
   DBuf<int64_t> s_cts;
   DBuf<unsigned char> s_keys, s_keys2;
   DBuf<int32_t> s_part, s_fst, s_relay, s_rfail;
   DBuf<uint8_t> s_dec2;  // selective fame widening: the new layout's decisions
-  bool minw_full = true;   // d_minw's rows are stale: the next rounds tail recomputes all
-  // coordinate sweeps: transposed tables and scratch
-  int n_sweeps = 0;
-  DBuf<int32_t> d_FDT, s_chg, s_bar, s_dirty;
+  // coordinate sweeps: scratch
+  DBuf<int32_t> s_chg, s_bar, s_dirty;
   DBuf<int32_t> s_src;  // hge_consensus_timestamp_sources: ids, then their sources
   // windowed lastAncestors (hge_coords_win.hip): chunk plans, row sums, starting rows
   DBuf<int4> s_lwplan;
   DBuf<uint32_t> s_lwsum, s_lwinit;
   DBuf<int32_t> s_lwpos, s_lwrisky;
-  int ncu_cache = 0;
+  DBuf<int32_t> s_fdlo;     // [2N]: the first position to refresh per chain, then the chains' lengths
+  DBuf<uint64_t> s_gran;
+  DBuf<int32_t> s_bseg;
+  DBuf<uint64_t> s_H;                // speculative walk: epoch-tagged histories
+  DBuf<int32_t> s_hn, s_hres;        // rows written + progress hints, merge results
+  DBuf<uint64_t> s_cH, s_cS, s_cT, s_cM;  // speculative wide walk: rows, ssc bits, tables, merges
+  DBuf<uint32_t> s_mb;                    // direct rounds: staged member rows (two parity blocks)
+  DBuf<int32_t> s_cn;
+  // consensus control block (one upload) and results block (one readback)
+  DBuf<int32_t> s_cctl, s_out;
+  // the coordinate step's control block (hge_plan::CoordsCtl, bound in CoordStep)
+  DBuf<int32_t> s_kctl;
+  DBuf<uint64_t> s_dbg;   // diagnostic stamps (HGE_STAMPS=1)
+  DBuf<uint64_t> s_wdbg;  // HGE_WALK_DEBUG: the walkers' cycle stamps
+  // cross-GPU split: a walker's rows (hge_frontier_walk), the exchange of an emulated
+  // part, every part's ordered ids and their offsets
+  DBuf<int32_t> s_hist, s_hstate;
+  DBuf<uint64_t> s_hssc;
+  DBuf<uint8_t> s_xbuf;
+  DBuf<int32_t> s_sord;
+  DBuf<int64_t> s_soff;
+  // The walk's select-path counters (hge_walk_select_paths): two slots of {narrow, exact},
+  // cleared once.  Walk k adds to slot k & 1 and clears the other slot as it ends,
+  // for the walk after it on the stream: no clearing launch per walk (an online call is a
+  // few hundred microseconds, a memset node was ~10 of them).
+  DBuf<unsigned long long> s_wpaths;
+  // The order stage's sort-path counters (hge_sort_paths): two slots of {packed, index,
+  // k_bucket_sort_big's next bucket, unused}, handed over like the walk's.  An order stage
+  // without a bucket past 512 keys launches no counting kernel and reports (0, 0).
+  DBuf<unsigned long long> s_spaths;
+
+  // ---- stream lifetime: fresh at hge_reset and hge_replay_prepare (reset_state) ----
+  struct StreamState {
+    // the accepted events and the admission state; log.chain_limit is the longest chain
+    // of the uint16 wide path (then: to_wide32)
+    HostLog log;
+    int64_t n_dev = 0;  // uploaded
+    // a packed upload of the events [up_n0, up_n1) waiting for k_chain_fill (upload())
+    std::vector<UpEv> h_up;  // the packed records, uploaded with coords_a's control block
+    int64_t up_n0 = -1, up_n1 = -1;
+    // N > 32 past chain_limit: int32 positions for good (hge_wide32.hip); pending until
+    // the next coordinate step converts the packed table.  A new stream starts packed.
+    bool wide32 = false, wide32_pending = false;
+    // to_wide32's progress bits: 1 the runs widened, 2 the FD rows, 4 the int32 LA table allocated
+    int w32_done = 0;
+    // what failed, when an internal failure left the host and device state apart (empty:
+    // none): every later consensus call refuses (HGE_ERR_INTERNAL) until a new stream
+    std::string failed;
+    int R_set = 0;  // rounds recorded by hge_set_round (Store.SetRound)
+    std::vector<int64_t> replay_calls;  // n_c per call (accepted counts)
+    // a plan belongs to the stream it was made for (it is checked against replay_calls)
+    SplitPlan sp;
+    bool sp_active = false;  // during hge_split_run
+    // hge_replay_run: this replay's coordinate step may skip the timestamps.  Set around
+    // replay_begin, which assigns the consensus part: so it lives here.
+    bool rows_bulk = false;
+    StreamState() = default;
+    StreamState(int n, int32_t chain_limit) : log(n, chain_limit) {}
+  } strm;
+
+  // ---- consensus lifetime: fresh at the two above and at every replay (replay_begin) ----
+  struct ConsensusState {
+    int64_t n_coords = 0;     // coordinates + rounds computed
+    int64_t n_divided = 0;    // visible to DecideFame / FindOrder (DivideRounds)
+    std::vector<int32_t> coords_len;  // chain lengths at n_coords
+    int R = 0;                // Store.Rounds()
+    int R_div = 0;            // Rounds() as seen by the consensus calls (DivideRounds)
+    std::vector<int32_t> h_minw;  // first witness id per round (read back by coords)
+    bool minw_full = true;   // d_minw's rows are stale: the next rounds tail recomputes all
+    int lcr = -1;             // LastConsensusRound (-1 nil)
+    int lcre = 0;             // LastCommitedRoundEvents
+    int64_t ctx = 0;          // ConsensusTransactions
+    std::vector<int32_t> consensus;  // the consensus log (unbounded)
+    int64_t cons_pin_n = 0;   // ... and its tail still in the pinned order buffer (pin_ord)
+    bool lazy_order = false;  // during a replay's batch: the order goes to pin_ord
+    int64_t n_und = 0;
+    bool und_fresh = false;  // the candidate list is every event of a fresh replay
+    // the candidates' lowest round, read back with the round count (coords_b) for the
+    // undetermined list of n_und = key[0] + key[2] - key[1] events after the divide
+    // that raises n_divided from key[1] to key[2] (key[0] < 0: none)
+    int32_t mnr_pre = 0;
+    int64_t mnr_key[3] = {-1, 0, 0};
+    std::optional<CoordStep> cstep;  // the pending coordinate step
+    bool dividing = false, und_appended = false;  // DivideRounds in progress (divide)
+    // cross-GPU split: the joined frontier rows of the walkers (hge_split_finish)
+    bool ext_on = false, ext_natural = false;
+    int ext_rows = 0;
+    std::vector<int32_t> ext_C;
+    std::vector<uint64_t> ext_ssc;
+    // A fresh bulk replay at uint16 positions writes the FD rows alone (k_fd_rows16) and
+    // takes its median from them (k_median_rows): d_FDTD / d_FDTW then hold no row of the
+    // current coordinates (fdtd_stale) until k_fd_transpose_ts has run over the positions a
+    // reader needs.  Every reader of the two tables calls ensure_fdtd() first; the replay
+    // itself ends with that pass over the still-undetermined events' rows (fdtd_tail).
+    bool fdtd_stale = false;
+    int fdtd_maxlen = 0;      // the longest chain of the stale coordinates
+    std::vector<int64_t> replay_counts;  // the last replay's per-call batches
+    int x_iter = 0;  // fame iteration of the current batch (the emulation record's index)
+    bool vis_all = false;  // this batch: one call seeing every event (no visibility table)
+    std::chrono::steady_clock::time_point w_start;  // the replay's start (hge_stage_times)
+    // the consensus control block's regions in s_cctl (bind_ctl, every batch)
+    int64_t* c_nc = nullptr;
+    int32_t *c_Rc = nullptr, *c_Lc = nullptr, *c_flags = nullptr, *c_pr = nullptr, *c_pidx = nullptr;
+    int32_t* c_sgo = nullptr;
+    const int32_t* segoff_p = nullptr;  // segment offsets used by k_round_received
+    ConsensusState() = default;
+    explicit ConsensusState(int n) : coords_len(n, 0) {}
+  } cons;
+
+  // ==== end of state: member functions only from here on (and the step structs) ====
+
+  int64_t consensus_size() const { return (int64_t)cons.consensus.size() + cons.cons_pin_n; }
+  void consensus_sync() {
+    if (!cons.cons_pin_n) return;
+    cons.consensus.insert(cons.consensus.end(), pin_ord.p, pin_ord.p + cons.cons_pin_n);
+    cons.cons_pin_n = 0;
+  }
+  void ensure_pin_ord(size_t n) {
+    if (n <= pin_ord.n && pin_ord.p) return;
+    consensus_sync();
+    pin_ord_dev = nullptr;
+    pin_ord.need(std::max<size_t>(n, 1));
+    pin_ord_dev = PinnedMem::device_ptr(pin_ord.p);
+  }
   int n_cu() {
     if (!ncu_cache) HGE_HIPCHK(hipDeviceGetAttribute(&ncu_cache, hipDeviceAttributeMultiprocessorCount, device));
     return ncu_cache;
   }
-  DBuf<int32_t> d_FDTD;  // N > 16: timestamp offsets at the FD positions (the wide median)
-  DBuf<uint8_t> d_FDTW;  // N > 16: per (row, 64-column tile) out-of-range flags of d_FDTD
-  // A fresh bulk replay at uint16 positions writes the FD rows alone (k_fd_rows16) and
-  // takes its median from them (k_median_rows): d_FDTD / d_FDTW then hold no row of the
-  // current coordinates (fdtd_stale) until k_fd_transpose_ts has run over the positions a
-  // reader needs.  Every reader of the two tables calls ensure_fdtd() first; the replay
-  // itself ends with that pass over the still-undetermined events' rows (fdtd_tail).
-  bool rows_bulk = false;   // hge_replay_run: this replay's coordinate step may skip the timestamps
-  bool fdtd_stale = false;
-  int fdtd_maxlen = 0;      // the longest chain of the stale coordinates
-  DBuf<int32_t> s_fdlo;     // [2N]: the first position to refresh per chain, then the chains' lengths
-  // test hook (HGE_TEST_MEDIAN_ROWS_FALLBACK=1): the coordinate step skips the timestamps
-  // but the median takes k_median_wave, so ensure_fdtd()'s full pass runs
-  bool test_rows_fallback = getenv("HGE_TEST_MEDIAN_ROWS_FALLBACK") != nullptr;
-  DBuf<int32_t> d_WLA;   // N > 16: round frontier rows transposed (k_witness_la)
-  DBuf<uint16_t> d_WLR;  // N > 64, packed path: the same rows row-major as LA + 1 (theta)
-  DBuf<uint64_t> d_ssc, s_gran;
-  DBuf<int32_t> s_bseg;
-  DBuf<uint64_t> s_H;                // speculative walk: epoch-tagged histories
-  DBuf<int32_t> s_hn, s_hres;        // rows written + progress hints, merge results
-  uint32_t walk_epoch = 0;
-  int walk_chk[2] = {448, 2};        // checker threads, poll pause
-  bool coop_checked = false;
-  int coop_nb = 0, coop_ncu = 0, coop_spec_nb = -1, coop_spec_bs = 0;
   const void* coop_spec_fn() const {
     return coop_spec_bs == 1024 ? (const void*)k_rounds_coop_spec<1024> : (const void*)k_rounds_coop_spec<512>;
   }
-  DBuf<uint64_t> s_cH, s_cS, s_cT, s_cM;  // speculative wide walk: rows, ssc bits, tables, merges
-  DBuf<uint32_t> s_mb;                    // direct rounds: staged member rows (two parity blocks)
-  DBuf<int32_t> s_cn;
-  uint32_t coop_epoch = 0;
-
-  Event ev[8];
-  // per-kernel HIP-event timing on the engine stream (hge_set_profiling)
-  bool prof_on = false;
-  std::vector<Event> prof_pool;
-  std::vector<std::pair<std::string, int>> prof_rec;
-  std::vector<std::string> prof_names;
-  std::vector<double> prof_ms;
-  std::vector<int64_t> prof_cnt;
-  int R_div = 0;            // Rounds() as seen by the consensus calls (DivideRounds)
-  std::vector<int32_t> h_minw;  // first witness id per round (read back by coords)
-  // consensus control block (one upload) and results block (one readback)
-  DBuf<int32_t> s_cctl, s_out;
-  std::vector<int32_t> h_cctl;
-  int64_t* c_nc = nullptr;
-  int32_t *c_Rc = nullptr, *c_Lc = nullptr, *c_flags = nullptr, *c_pr = nullptr, *c_pidx = nullptr;
-  int32_t* c_sgo = nullptr;
-  const int32_t* segoff_p = nullptr;  // segment offsets used by k_round_received
-  // the coordinate step's control block (hge_plan::CoordsCtl, bound in CoordStep) and its host staging
-  DBuf<int32_t> s_kctl;
-  std::vector<int32_t> h_kctl;
-  std::vector<hge_plan::Seg> h_segs;
-  bool und_fresh = false;  // the candidate list is every event of a fresh replay
-  float stage_ms[7] = {};
 
   Tables tables() const {
     Tables t;
@@ -284,7 +359,7 @@ struct hge_engine {
     t.FDTW = d_FDTW.p;
     t.WLA = wla16() ? nullptr : d_WLA.p;
     t.WLA16 = wla16() ? (uint16_t*)d_WLA.p : nullptr;
-    t.WLR = (N > 64 && !wide32) ? d_WLR.p : nullptr;
+    t.WLR = (N > 64 && !strm.wide32) ? d_WLR.p : nullptr;
     t.round = d_round.p;
     t.wit = d_wit.p;
     t.C = d_C.p;
@@ -305,16 +380,12 @@ struct hge_engine {
     HGE_HIPCHK(hipSetDevice(device));
     st.create();
     for (auto& e : ev) e.create();
-    chain_len.assign(N, 0);
-    chain_last.assign(N, -1);
-    h_chain.assign(N, {});
     // the wide kernels keep chain positions as uint16 (LA16, the rounds walk, theta):
     // a longer chain switches the engine to int32 positions (to_wide32).
     // HGE_CHAIN_LIMIT (tests) lowers the switch point.
-    chain_limit = N > 32 ? 0xFFFE : INT32_MAX;
-    if (const char* cl = getenv("HGE_CHAIN_LIMIT")) chain_limit = std::max(1, std::min(chain_limit, atoi(cl)));
-    chain_limit0 = chain_limit;
-    coords_len.assign(N, 0);
+    chain_limit0 = hge_hooks::chain_limit(N > 32 ? 0xFFFE : INT32_MAX);
+    strm = StreamState(N, chain_limit0);
+    cons = ConsensusState(N);
     // chain tables: a creator's chain is ~cap/N long (binomial, sd ~ sqrt(cap/N));
     // rounds: a round spans >= ~4N events in gossip.  Both grow on demand.
     const int64_t c0 = std::max<int64_t>(cap, 1024);
@@ -324,42 +395,8 @@ struct hge_engine {
     s_small.need(16);
   }
 
-  void prof_begin(const char* name) {
-    if (!prof_on) return;
-    const int slot = (int)prof_rec.size() * 2;
-    while ((int)prof_pool.size() < slot + 2) {
-      prof_pool.emplace_back();
-      prof_pool.back().create();
-    }
-    HGE_HIPCHK(hipEventRecord(prof_pool[slot], st));
-    prof_rec.push_back({name, slot});
-  }
-  void prof_end() {
-    if (!prof_on) return;
-    HGE_HIPCHK(hipEventRecord(prof_pool[prof_rec.back().second + 1], st));
-  }
-  void prof_collect() {
-    if (prof_rec.empty()) return;
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    for (auto& r : prof_rec) {
-      float ms = 0;
-      HGE_HIPCHK(hipEventElapsedTime(&ms, prof_pool[r.second], prof_pool[r.second + 1]));
-      size_t k = 0;
-      while (k < prof_names.size() && prof_names[k] != r.first) k++;
-      if (k == prof_names.size()) {
-        prof_names.push_back(r.first);
-        prof_ms.push_back(0);
-        prof_cnt.push_back(0);
-      }
-      prof_ms[k] += ms;
-      prof_cnt[k] += 1;
-    }
-    prof_rec.clear();
-  }
 
   // diagnostic stamps (HGE_STAMPS=1): per-section cycle counters of some kernels
-  DBuf<uint64_t> s_dbg;
-  bool dbg_on = getenv("HGE_STAMPS") != nullptr;
   uint64_t* dbg_p() {
     if (!dbg_on) return nullptr;
     if (!s_dbg.p) {
@@ -381,7 +418,7 @@ struct hge_engine {
   // events free themselves, the stream last) and the HGE_HOST_PHASES line
   ~hge_engine() {
     if (st) (void)hipStreamSynchronize(st);
-    if (getenv("HGE_HOST_PHASES") && hp.calls) {
+    if (hge_hooks::host_phases() && hp.calls) {
       const double c = (double)hp.calls;
       fprintf(stderr,
               "{\"hge_host_phases\": {\"calls\": %lld, \"launches_per_call\": %.2f, \"copies_per_call\": %.2f, "
@@ -394,19 +431,19 @@ struct hge_engine {
   void ensure_events(int64_t m) {
     if (m <= Ecap) return;
     int64_t cap = std::max<int64_t>(m, Ecap + Ecap / 2);
-    d_creator.grow_keep(cap, n_dev, st);
-    d_index.grow_keep(cap, n_dev, st);
-    d_sp.grow_keep(cap, n_dev, st);
-    d_op.grow_keep(cap, n_dev, st);
-    d_ntx.grow_keep(cap, n_dev, st);
-    d_ts.grow_keep(cap, n_dev, st);
-    d_S.grow_keep(4 * cap, 4 * n_dev, st);
-    d_coin.grow_keep(cap, n_dev, st);
-    d_round.grow_keep(cap, n_coords, st);
-    d_wit.grow_keep(cap, n_coords, st);
-    d_rr.grow_keep(cap, n_coords, st, 0xFF);
-    d_cts.grow_keep(cap, n_coords, st, 0);
-    d_und.grow_keep(cap, n_und, st);
+    d_creator.grow_keep(cap, strm.n_dev, st);
+    d_index.grow_keep(cap, strm.n_dev, st);
+    d_sp.grow_keep(cap, strm.n_dev, st);
+    d_op.grow_keep(cap, strm.n_dev, st);
+    d_ntx.grow_keep(cap, strm.n_dev, st);
+    d_ts.grow_keep(cap, strm.n_dev, st);
+    d_S.grow_keep(4 * cap, 4 * strm.n_dev, st);
+    d_coin.grow_keep(cap, strm.n_dev, st);
+    d_round.grow_keep(cap, cons.n_coords, st);
+    d_wit.grow_keep(cap, cons.n_coords, st);
+    d_rr.grow_keep(cap, cons.n_coords, st, 0xFF);
+    d_cts.grow_keep(cap, cons.n_coords, st, 0);
+    d_und.grow_keep(cap, cons.n_und, st);
     Ecap = cap;
   }
 
@@ -465,48 +502,24 @@ struct hge_engine {
     // + round count, overflow flag, lowest candidate round, hand-off error and up to 16
     // partial lowest rounds (k_round_minw)
     d_minw.need(nr + 20);
-    minw_full = true;  // (need() does not keep the rows' first witnesses)
+    cons.minw_full = true;  // (need() does not keep the rows' first witnesses)
     // C must be INF32 beyond the old rows
     fill_i32(d_C.p + oldn, (int64_t)(nr - Rcap) * N, INF32);
     sync();
     Rcap = (int)nr;
   }
 
+  // a new stream (hge_reset, hge_replay_prepare): fresh stream and consensus parts, and
+  // the device tables a stream starts from
   void reset_state() {
     sync();
-    failed.clear();  // a new stream (hge_reset, hge_replay_prepare)
-    minw_full = true;
-    cons_pin_n = 0;
-    h_creator.clear();
-    h_index.clear();
-    h_sp.clear();
-    h_op.clear();
-    h_ntx.clear();
-    h_ts.clear();
-    h_S.clear();
-    h_coin.clear();
-    chain_len.assign(N, 0);
-    chain_last.assign(N, -1);
-    h_chain.assign(N, {});
-    coords_len.assign(N, 0);
-    n_events = n_dev = n_coords = n_divided = 0;
-    up_n0 = up_n1 = -1;
-    h_up.clear();
-    R = 0;
-    R_set = 0;
-    h_minw.clear();
-    lcr = -1;
-    lcre = 0;
-    ctx = 0;
-    consensus.clear();
-    n_und = 0;
-    wide32 = wide32_pending = false;  // a new stream starts on the packed path
-    w32_done = 0;
-    chain_limit = chain_limit0;
+    strm = StreamState(N, chain_limit0);
+    cons = ConsensusState(N);
     reset_rounds();
     HGE_HIPCHK(hipMemsetAsync(d_chain.p, 0xFF, (size_t)N * ccap * 4, st));
     sync();
   }
+
 
   // fresh per-round tables (C, W, bitsets, fame, counts) and received rounds: one launch
   void reset_rounds() {
@@ -516,127 +529,58 @@ struct hge_engine {
             nbits, Ecap, d_rr.p);
   }
 
-  // ---------------- admission (hashgraph.go:366-396) ----------------
+  // ---------------- admission (hashgraph.go:366-396, hge_hostlog.h) ----------------
+  // The log checks the event; the one device question is the engine's: a chain at the
+  // limit of the uint16 positions goes on in int32 if the int32 table fits.
   int admit(const hge_event& e, int32_t sp, int32_t op) {
-    const int c = e.creator;
-    if (c < 0 || c >= N) {
-      err = "Could not find fake creator id";
-      return HGE_ERR_CREATOR;
+    HostLog& log = strm.log;
+    const int r = log.admit(e, sp, op, err);
+    if (r != HostLog::kAtLimit) return r;
+    if (!(N > 32 && N <= 256 && !strm.wide32)) return log.capacity_error(err);
+    // past the uint16 positions: int32 from here on
+    // the int32 LA table must fit beside what is allocated: else refuse
+    // the event here (the stream stops, as at any rejection) rather than lift
+    // the cap and fail at the next coordinate step
+    // to_wide32's peak: the int32 LA table, plus (uint16 runs and FD rows) one
+    // int32 table being widened while the other's old copy is still held
+    size_t free_b = 0, total_b = 0;
+    const size_t tab = sizeof(int32_t) * (size_t)N * N * (size_t)std::max(ccap, log.chain_len[e.creator] + 2);
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < (fdt16() ? 2 : 1) * tab + (64u << 20)) {
+      err = "Chain capacity exceeded: the int32 position tables past 65,534 events per creator do not fit";
+      return HGE_ERR_CAPACITY;
     }
-    const int known = chain_len[c];
-    if (sp == HGE_NONE && op == HGE_NONE && known == 0) {
-      if (e.index != 0) {
-        err = "Event index does not match the creator's chain position";
-        return HGE_ERR_INDEX;
-      }
-      return HGE_OK;
-    }
-    if (sp < 0 || sp >= n_events) {
-      err = "Self-parent not known";
-      return HGE_ERR_SELF_PARENT_UNKNOWN;
-    }
-    if (h_creator[sp] != c) {
-      err = "Self-parent has different creator";
-      return HGE_ERR_SELF_PARENT_CREATOR;
-    }
-    if (op < 0 || op >= n_events) {
-      err = "Other-parent not known";
-      return HGE_ERR_OTHER_PARENT_UNKNOWN;
-    }
-    if (sp != chain_last[c]) {
-      err = "Self-parent not last known event by creator";
-      return HGE_ERR_SELF_PARENT_NOT_LAST;
-    }
-    if (e.index != known) {
-      err = "Event index does not match the creator's chain position";
-      return HGE_ERR_INDEX;
-    }
-    if (known >= chain_limit) {
-      if (N > 32 && N <= 256 && !wide32) {  // past the uint16 positions: int32 from here on
-        // the int32 LA table must fit beside what is allocated: else refuse
-        // the event here (the stream stops, as at any rejection) rather than lift
-        // the cap and fail at the next coordinate step
-        // to_wide32's peak: the int32 LA table, plus (uint16 runs and FD rows) one
-        // int32 table being widened while the other's old copy is still held
-        size_t free_b = 0, total_b = 0;
-        const size_t tab = sizeof(int32_t) * (size_t)N * N * (size_t)std::max(ccap, known + 2);
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < (fdt16() ? 2 : 1) * tab + (64u << 20)) {
-          err = "Chain capacity exceeded: the int32 position tables past 65,534 events per creator do not fit";
-          return HGE_ERR_CAPACITY;
-        }
-        wide32_pending = true;
-        chain_limit = INT32_MAX;
-      } else {
-        err = "Chain capacity exceeded: at most " + std::to_string(chain_limit) + " events per creator";
-        return HGE_ERR_CAPACITY;
-      }
-    }
+    strm.wide32_pending = true;
+    log.chain_limit = INT32_MAX;
     return HGE_OK;
   }
 
-  void append(const hge_event& e, int32_t sp, int32_t op) {
-    const int64_t id = n_events++;
-    h_creator.push_back(e.creator);
-    h_index.push_back(e.index);
-    h_sp.push_back(sp);
-    h_op.push_back(op);
-    h_ntx.push_back(e.n_tx);
-    h_ts.push_back(e.timestamp_ns);
-    for (int k = 0; k < 4; k++) {
-      uint64_t v = 0;
-      for (int b = 0; b < 8; b++) v = (v << 8) | e.s[8 * k + b];
-      h_S.push_back(v);
-    }
-    h_coin.push_back(e.hash[16] != 0 ? 1 : 0);
-    h_chain[e.creator].push_back((int32_t)id);
-    chain_len[e.creator]++;
-    chain_last[e.creator] = (int32_t)id;
-  }
 
-  // a packed upload of the events [up_n0, up_n1) waiting for k_chain_fill (upload())
-  std::vector<UpEv> h_up;  // the packed records, uploaded with coords_a's control block
-  int64_t up_n0 = -1, up_n1 = -1;
   void upload() {
-    if (n_dev == n_events) return;
-    ensure_events(n_events);
-    int maxlen = 0;
-    for (int c = 0; c < N; c++) maxlen = std::max(maxlen, chain_len[c]);
-    ensure_ccap(maxlen + 1);
-    const int64_t a = n_dev, m = n_events - n_dev;
-    if (m <= 16384 && a == n_coords) {
+    if (strm.n_dev == strm.log.n_events) return;
+    ensure_events(strm.log.n_events);
+    ensure_ccap(strm.log.max_chain() + 1);
+    const int64_t a = strm.n_dev, m = strm.log.n_events - strm.n_dev;
+    if (m <= 16384 && a == cons.n_coords) {
       // a small batch (an online call): one packed record per event through the
       // pinned arena, unpacked by the coordinate step's k_chain_fill (eight copies
       // from pageable memory were ~25 us of an online call)
-      std::vector<UpEv> up((size_t)m);
-      if (up_n0 >= 0) throw Error(HGE_ERR_INTERNAL, "packed upload pending twice");
-      for (int64_t i = 0; i < m; i++) {
-        UpEv& r = up[(size_t)i];
-        const size_t x = (size_t)(a + i);
-        r.creator = h_creator[x];
-        r.index = h_index[x];
-        r.sp = h_sp[x];
-        r.op = h_op[x];
-        r.ntx = h_ntx[x];
-        r.coin = h_coin[x];
-        r.ts = h_ts[x];
-        for (int k = 0; k < 4; k++) r.S[k] = h_S[4 * x + k];
-      }
+      if (strm.up_n0 >= 0) throw Error(HGE_ERR_INTERNAL, "packed upload pending twice");
       // (they travel with the coordinate step's control block: one copy for both)
-      h_up.swap(up);
-      up_n0 = a;
-      up_n1 = n_events;
-      n_dev = n_events;
+      strm.h_up = strm.log.pack(a, m);
+      strm.up_n0 = a;
+      strm.up_n1 = strm.log.n_events;
+      strm.n_dev = strm.log.n_events;
       return;
     }
-    HGE_HIPCHK(hipMemcpyAsync(d_creator.p + a, h_creator.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HGE_HIPCHK(hipMemcpyAsync(d_index.p + a, h_index.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HGE_HIPCHK(hipMemcpyAsync(d_sp.p + a, h_sp.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HGE_HIPCHK(hipMemcpyAsync(d_op.p + a, h_op.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HGE_HIPCHK(hipMemcpyAsync(d_ntx.p + a, h_ntx.data() + a, 4 * m, hipMemcpyHostToDevice, st));
-    HGE_HIPCHK(hipMemcpyAsync(d_ts.p + a, h_ts.data() + a, 8 * m, hipMemcpyHostToDevice, st));
-    HGE_HIPCHK(hipMemcpyAsync(d_S.p + 4 * a, h_S.data() + 4 * a, 32 * m, hipMemcpyHostToDevice, st));
-    HGE_HIPCHK(hipMemcpyAsync(d_coin.p + a, h_coin.data() + a, m, hipMemcpyHostToDevice, st));
-    n_dev = n_events;
+    HGE_HIPCHK(hipMemcpyAsync(d_creator.p + a, strm.log.h_creator.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_index.p + a, strm.log.h_index.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_sp.p + a, strm.log.h_sp.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_op.p + a, strm.log.h_op.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_ntx.p + a, strm.log.h_ntx.data() + a, 4 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_ts.p + a, strm.log.h_ts.data() + a, 8 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_S.p + 4 * a, strm.log.h_S.data() + 4 * a, 32 * m, hipMemcpyHostToDevice, st));
+    HGE_HIPCHK(hipMemcpyAsync(d_coin.p + a, strm.log.h_coin.data() + a, m, hipMemcpyHostToDevice, st));
+    strm.n_dev = strm.log.n_events;
   }
 
   void fill_iota(int32_t* p, int64_t n, int32_t base) {
@@ -647,108 +591,23 @@ struct hge_engine {
     if (n > 0) KLAUNCH(k_fill_i32, dim3(div_up(n, 256)), dim3(256), 0, st, p, n, v);
   }
 
-  // ---- host <-> device staging through pinned memory ----
-  // A copy from pageable memory makes the runtime wait for the stream, so every
-  // small control upload would be a hidden round trip.  Control data goes through
-  // a pinned arena instead: uploads are enqueued without waiting, downloads are
-  // queued and land in their host destinations at the next sync(), which also
-  // recycles the arena (everything enqueued before it has completed).
-  PBuf<char> pin;
-  size_t pin_used = 0;
-  struct Pending {
-    void* dst;
-    size_t off, bytes;
-  };
-  std::vector<Pending> pending;
-
-  char* pin_take(size_t bytes) {
-    const size_t need = (bytes + 255) & ~(size_t)255;
-    if (pin_used + need > pin.n) {
-      sync();
-      if (need > pin.n) pin.need(std::max<size_t>(need, std::max<size_t>(2 * pin.n, 1 << 16)));
-    }
-    char* q = pin.p + pin_used;
-    pin_used += need;
-    return q;
-  }
-  void h2d(void* dev, const void* host, size_t bytes) {
-    if (!bytes) return;
-    char* q = pin_take(bytes);
-    memcpy(q, host, bytes);
-    hp.copies++;
-    HGE_HIPCHK(hipMemcpyAsync(dev, q, bytes, hipMemcpyHostToDevice, st));
-  }
-  void d2h(void* host, const void* dev, size_t bytes) {
-    if (!bytes) return;
-    char* q = pin_take(bytes);
-    hp.copies++;
-    HGE_HIPCHK(hipMemcpyAsync(q, dev, bytes, hipMemcpyDeviceToHost, st));
-    pending.push_back({host, (size_t)(q - pin.p), bytes});
-  }
-  // download into the arena itself: the returned offset stays readable after the
-  // next sync() until the arena is used again (no second host copy)
-  size_t d2h_pinned(const void* dev, size_t bytes) {
-    char* q = pin_take(bytes);
-    if (bytes) hp.copies++;
-    if (bytes) HGE_HIPCHK(hipMemcpyAsync(q, dev, bytes, hipMemcpyDeviceToHost, st));
-    return (size_t)(q - pin.p);
-  }
-  int64_t n_syncs = 0;  // host waits on the stream (hge_host_syncs)
-  // where an online call's host time goes (HGE_HOST_PHASES=1: printed at destroy):
-  // calls, launches, copies, ns spent inside hipStreamSynchronize, ns in the calls
-  struct HostPhases {
-    int64_t calls = 0, launches = 0, copies = 0, wait_ns = 0, call_ns = 0, insert_ns = 0;
-  } hp;
-  static int64_t now_ns() {
-    return std::chrono::duration_cast<std::chrono::nanoseconds>(
-               std::chrono::steady_clock::now().time_since_epoch()).count();
-  }
-  void sync() {
-    n_syncs++;
-    const int64_t w0 = now_ns();
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    hp.wait_ns += now_ns() - w0;
-    for (const Pending& pd : pending) memcpy(pd.dst, pin.p + pd.off, pd.bytes);
-    pending.clear();
-    pin_used = 0;
-  }
+  // ---- host <-> device staging through the pinned arena (hge_xfer.h) ----
+  // (forwarders: some eighty call sites, here and in the C ABI, name these)
+  void h2d(void* dev, const void* host, size_t bytes) { xfer.h2d(dev, host, bytes); }
+  void d2h(void* host, const void* dev, size_t bytes) { xfer.d2h(host, dev, bytes); }
+  size_t d2h_pinned(const void* dev, size_t bytes) { return xfer.d2h_pinned(dev, bytes); }
+  void sync() { xfer.sync(); }
   template <typename F>
   void readback(F* host, const F* dev, size_t n) {
-    d2h(host, dev, n * sizeof(F));
-    sync();
+    xfer.readback(host, dev, n);
   }
+
 
   // ---------------- coordinates + rounds for [n_coords, n_events) ----------------
   // coords_a (the control block, lastAncestors, firstDescendants) then coords_b (the
   // rounds frontier and what follows).  What their stages share is a CoordStep: coords_a
   // makes it, coords_b (or online_fast) takes it, and in between the step is pending
   // (cstep has a value): the cross-GPU split (hge_split_*) runs a walker there.
-  struct CoordStep {
-    bool fresh = false;      // nothing had coordinates or rounds before
-    int64_t n0 = 0, n1 = 0;  // the new ids
-    int maxnew = 0;          // most new positions on one chain, + 1
-    int tot0 = 0;            // a fresh walk's fss rows (every chain's length)
-    int SEG = 0, nseg = 0;   // the sweeps' segment length and count
-    int maxlen = 0, minlen = 0;  // the longest and the shortest chain
-    enum class La { Windows, Seq, Sweeps } la = La::Sweeps;  // how lastAncestors are computed
-    // the control block's regions in s_kctl (bind_kctl)
-    int32_t *rstate = nullptr, *olen = nullptr, *len = nullptr, *plo = nullptr, *qlo = nullptr;
-    int32_t *fss_lo = nullptr, *fss_off = nullptr, *fss_total = nullptr, *segbase = nullptr;
-    const int2* segs = nullptr;
-    int32_t *cand_lo = nullptr, *cand_hi = nullptr;  // a split part's candidates (else null)
-    int32_t* risky1 = nullptr;  // the one-window lastAncestors pass's risky id (-1 as uploaded)
-    const UpEv* up = nullptr;   // the chain-table fill's source: the packed upload, or null (the tables)
-    UpDst up_dst{};
-    // what earlier kernels of the step did already
-    bool frontier_started = false;  // k_frontier_start's block (k_chain_fill_qlo, k_la_seq)
-    bool qlo_done = false;          // k_fd_qlo's blocks (the same two)
-    bool fd_done = false;           // the FD rows and FDT runs (k_la_seq, N <= 16)
-    // the FD rows without their timestamp offsets (k_fd_rows16): a fresh bulk replay whose
-    // median reads the rows itself (k_median_rows)
-    bool fd_rows_only = false;
-    bool take_frontier_start() { return std::exchange(frontier_started, false); }  // (a later attempt starts again)
-  };
-  std::optional<CoordStep> cstep;
   // what one attempt's rounds walk did besides walking
   struct Walk {
     bool assigned = false;   // the new events' rounds (k_round_assign's work)
@@ -767,51 +626,14 @@ struct hge_engine {
     s.risky1 = p + L.risky;
     s.up = L.up_words ? (const UpEv*)(p + L.up) : nullptr;
   }
-  std::chrono::steady_clock::time_point w_start;
-  // cross-GPU split: the joined frontier rows of the walkers (hge_split_finish)
-  bool ext_on = false, ext_natural = false;
-  int ext_rows = 0;
-  std::vector<int32_t> ext_C;
-  std::vector<uint64_t> ext_ssc;
-  DBuf<int32_t> s_hist, s_hstate;
-  DBuf<uint64_t> s_hssc;
-  // One hashgraph sharded across GPUs by time (hge_split_plan, DESIGN.md §6): part
-  // p owns the events [a_p, a_{p+1}) and the calls [cb_p, cb_{p+1}).  Every part
-  // computes the coordinates and walks the rounds recurrence (sequential: it cannot
-  // be split exactly, DESIGN.md §6); part p then decides the fame of the rounds whose
-  // first witness it owns and commits the events its calls receive (candidates from
-  // cand_lo_p, the only FD timestamp rows it writes), and the parts exchange fame
-  // decisions and ordered slices through the caller's all-gather (hge_split_exchange).
-  struct SplitPlan {
-    int part = 0, nparts = 0;
-    std::vector<int64_t> a;     // event bounds, nparts + 1
-    std::vector<int32_t> cb;    // call bounds, nparts + 1
-    std::vector<int64_t> clo;   // first candidate of every part
-  } sp;
-  bool sp_active = false;  // during hge_split_run
-  bool split_on() const { return sp_active && sp.nparts > 1; }
-  hge_exchange_fn x_fn = nullptr;
-  void* x_ctx = nullptr;
-  // measurement aid (hge_split_emulate): an unsplit replay records what every part
-  // of a split contributes to the exchanges (the fame decisions of every fame
-  // iteration, the order, per-call batches, round received / timestamps, the
-  // undetermined list); a split part run without an exchange then takes the other
-  // parts' slots from the record, so one GPU times each part of a G-way split alone
-  bool rec_on = false, rec_have = false;
-  std::vector<std::vector<uint8_t>> rec_dec;
-  std::vector<int32_t> rec_order, rec_rr, rec_left;
-  std::vector<int64_t> rec_counts, rec_cts;
-  int x_iter = 0;  // fame iteration of the current batch (the record's index)
-  DBuf<uint8_t> s_xbuf;
+  bool split_on() const { return strm.sp_active && strm.sp.nparts > 1; }
   bool emulating() const { return split_on() && !x_fn && rec_have; }
-  DBuf<int32_t> s_sord;   // split: every part's ordered ids
-  DBuf<int64_t> s_soff;   // split: their offsets
   // a device buffer of nparts slots of `bytes` (the caller's memory: its collectives
   // write into it), then the all-gather: this part's slot is filled and the stream drained
   void* x_buf(int64_t bytes) {
     sync();  // the caller may hand out (or move) the memory of the previous exchange
     if (emulating()) {
-      s_xbuf.need((size_t)bytes * sp.nparts);
+      s_xbuf.need((size_t)bytes * strm.sp.nparts);
       return s_xbuf.p;
     }
     void* b = nullptr;
@@ -832,19 +654,14 @@ struct hge_engine {
       int lo = 0, hi = nr;
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        if ((int64_t)h_minw[pr_round[mid]] < ev) lo = mid + 1;
+        if ((int64_t)cons.h_minw[pr_round[mid]] < ev) lo = mid + 1;
         else hi = mid;
       }
       return lo;
     };
-    win_lo = g == 0 ? 0 : first_at(sp.a[g]);
-    win_hi = g == sp.nparts - 1 ? nr : first_at(sp.a[g + 1]);
+    win_lo = g == 0 ? 0 : first_at(strm.sp.a[g]);
+    win_hi = g == strm.sp.nparts - 1 ? nr : first_at(strm.sp.a[g + 1]);
   }
-  // the candidates' lowest round, read back with the round count (coords_b) for the
-  // undetermined list of n_und = key[0] + key[2] - key[1] events after the divide
-  // that raises n_divided from key[1] to key[2] (key[0] < 0: none)
-  int32_t mnr_pre = 0;
-  int64_t mnr_key[3] = {-1, 0, 0};
   void coords() {
     if (coords_a()) coords_b();
   }
@@ -858,23 +675,23 @@ struct hge_engine {
 
   // the step's first half; leaves it pending (cstep); false: no new event
   bool coords_a() {
-    cstep.reset();
+    cons.cstep.reset();
     upload();
-    if (wide32_pending) to_wide32();
-    if (n_events == n_coords) return false;
+    if (strm.wide32_pending) to_wide32();
+    if (strm.log.n_events == cons.n_coords) return false;
     CoordStep s;
     plan_step(s);
     const Tables t = tables();
     chain_fill(t, s);
     last_ancestors(t, s);
     first_descendants(t, s);
-    cstep = s;
+    cons.cstep = s;
     return true;
   }
   // the control block (hge_plan::CoordsCtl), one upload
   void plan_step(CoordStep& s) {
-    s.n0 = n_coords;
-    s.n1 = n_events;
+    s.n0 = cons.n_coords;
+    s.n1 = strm.log.n_events;
     // segment length: latency-bound sweeps (small N) like short segments, bandwidth-bound
     // ones (large N) long ones (fewer stale carries)
     s.SEG = N <= 32 ? 16 : 64;
@@ -885,43 +702,43 @@ struct hge_engine {
                                      : CoordStep::La::Sweeps;
     const bool sweeps = s.la == CoordStep::La::Sweeps;
     h_segs.clear();
-    if (sweeps) hge_plan::sweep_segments(h_segs, coords_len, chain_len, s.SEG);
+    if (sweeps) hge_plan::sweep_segments(h_segs, cons.coords_len, strm.log.chain_len, s.SEG);
     s.nseg = sweeps ? (int)h_segs.size() : 1;
-    s.fresh = R == 0;
+    s.fresh = cons.R == 0;
     s.minlen = INT32_MAX;
     for (int c = 0; c < N; c++) {
-      s.maxnew = std::max(s.maxnew, chain_len[c] - coords_len[c] + 1);
-      s.fresh = s.fresh && coords_len[c] == 0;
-      s.maxlen = std::max(s.maxlen, chain_len[c]);
-      s.minlen = std::min(s.minlen, chain_len[c]);
+      s.maxnew = std::max(s.maxnew, strm.log.chain_len[c] - cons.coords_len[c] + 1);
+      s.fresh = s.fresh && cons.coords_len[c] == 0;
+      s.maxlen = std::max(s.maxlen, strm.log.chain_len[c]);
+      s.minlen = std::min(s.minlen, strm.log.chain_len[c]);
     }
-    s.fd_rows_only = rows_bulk && s.fresh && s.n0 == 0 && fdt16() && !split_on() && !rec_on && !ext_on;
+    s.fd_rows_only = strm.rows_bulk && s.fresh && s.n0 == 0 && fdt16() && !split_on() && !rec_on && !cons.ext_on;
     std::vector<int32_t> cand;
     if (split_on()) {
       // FD timestamp rows (the median's input) of the ids [cand_lo, the part's end)
-      const int64_t A = sp.clo[sp.part], B = sp.a[sp.part + 1];
+      const int64_t A = strm.sp.clo[strm.sp.part], B = strm.sp.a[strm.sp.part + 1];
       cand.resize(2 * (size_t)N);
       for (int c = 0; c < N; c++) {
-        const std::vector<int32_t>& ch = h_chain[c];
+        const std::vector<int32_t>& ch = strm.log.h_chain[c];
         cand[c] = (int)(std::lower_bound(ch.begin(), ch.end(), (int32_t)A) - ch.begin());
         cand[N + c] = (int)(std::lower_bound(ch.begin(), ch.end(), (int32_t)B) - ch.begin());
       }
     }
     // the packed event records (an online call's upload) ride in the same copy
-    const bool packed = up_n0 == s.n0 && up_n1 == s.n1;
-    if (packed && h_up.empty()) throw Error(HGE_ERR_INTERNAL, "packed upload without records");
+    const bool packed = strm.up_n0 == s.n0 && strm.up_n1 == s.n1;
+    if (packed && strm.h_up.empty()) throw Error(HGE_ERR_INTERNAL, "packed upload without records");
     static_assert(sizeof(UpEv) % 4 == 0, "records are whole words");
     static_assert(sizeof(hge_plan::Seg) == sizeof(int2), "the kernels read segments as int2");
     const hge_plan::CoordsCtl L =
-        hge_plan::coords_ctl_layout(N, h_segs.size(), packed ? sizeof(UpEv) * h_up.size() / 4 : 0);
-    s.tot0 = hge_plan::fill_coords_ctl(h_kctl, L, R, coords_len, chain_len, h_segs, s.SEG, cand);
-    if (packed) memcpy(&h_kctl[L.up], h_up.data(), sizeof(UpEv) * h_up.size());
+        hge_plan::coords_ctl_layout(N, h_segs.size(), packed ? sizeof(UpEv) * strm.h_up.size() / 4 : 0);
+    s.tot0 = hge_plan::fill_coords_ctl(h_kctl, L, cons.R, cons.coords_len, strm.log.chain_len, h_segs, s.SEG, cand);
+    if (packed) memcpy(&h_kctl[L.up], strm.h_up.data(), sizeof(UpEv) * strm.h_up.size());
     s_kctl.need(h_kctl.size());
     h2d(s_kctl.p, h_kctl.data(), 4 * h_kctl.size());
     bind_kctl(s, L);
     s.up_dst = UpDst{d_creator.p, d_index.p, d_sp.p, d_op.p, d_ntx.p, d_ts.p, d_S.p, d_coin.p};
-    up_n0 = up_n1 = -1;
-    h_up.clear();
+    strm.up_n0 = strm.up_n1 = -1;
+    strm.h_up.clear();
   }
   // the chain table for the new ids, unless k_la_seq will fill it; past a fresh state
   // with k_fd_qlo's blocks and, for the wide rounds walk, k_frontier_start's
@@ -929,7 +746,7 @@ struct hge_engine {
     if (s.la == CoordStep::La::Seq) return;
     const int nfb = div_up((int)(s.n1 - s.n0), 256);
     if (!s.fresh && N <= 256) {
-      const bool fst = N > 32 && !wide32 && !frontier_fallback && !split_on() && !ext_on;
+      const bool fst = N > 32 && !strm.wide32 && !frontier_fallback && !split_on() && !cons.ext_on;
       if (fst) {
         s_fst.need(N + 1);
         s_bar.need(2);
@@ -950,15 +767,15 @@ struct hge_engine {
   // undetermined list) and, with `tail`, k_round_tail's work
   RoundAssign round_assign(const CoordStep& s, bool tail) {
     s_newwit.need(s.n1 - s.n0);
-    RoundAssign ra{(int)s.n0, (int)s.n1, s_newwit.p, s.rstate + 2, und_appended ? d_und.p + n_und : (int32_t*)nullptr};
+    RoundAssign ra{(int)s.n0, (int)s.n1, s_newwit.p, s.rstate + 2, cons.und_appended ? d_und.p + cons.n_und : (int32_t*)nullptr};
     if (tail) {
       ra.minw = d_minw.p;
       ra.G = wit_group();
       ra.und = d_und.p;
-      ra.n_und = (int)n_und;
-      ra.lo = (int)n_divided;
+      ra.n_und = (int)cons.n_und;
+      ra.lo = (int)cons.n_divided;
       ra.hi = (int)s.n1;
-      ra.r_from = minw_full ? 0 : -1;
+      ra.r_from = cons.minw_full ? 0 : -1;
       ra.rlo_dev = s_fst.p;
     }
     return ra;
@@ -969,14 +786,14 @@ struct hge_engine {
   // and walks again.
   enum class RoundsOutcome { Done, Grow, HandoffTimeout };
   void coords_b() {
-    CoordStep s = *cstep;
-    cstep.reset();
+    CoordStep s = *cons.cstep;
+    cons.cstep.reset();
     for (bool retry = false;; retry = true) {
       // the wide frontier grids stay on the device until the readback's sync: two such
       // grids on one device must not overlap (frontier_lock)
       std::unique_lock<std::mutex> flk;
       if (N > 32) flk = frontier_lock();
-      const int32_t rs[3] = {R, 0, 0};
+      const int32_t rs[3] = {cons.R, 0, 0};
       if (retry) h2d(s.rstate, rs, 12);
       const Walk w = walk_rounds(s);
       assign_rounds(s, w);
@@ -989,19 +806,19 @@ struct hge_engine {
         // are recomputed from scratch.
         frontier_fallback = true;
         n_frontier_fallbacks++;
-        HGE_HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(d_C.p + (size_t)R * N), INF32, (size_t)(Rcap - R) * N, st));
+        HGE_HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(d_C.p + (size_t)cons.R * N), INF32, (size_t)(Rcap - cons.R) * N, st));
       } else if (o == RoundsOutcome::Grow) {
         ensure_rcap((int64_t)Rcap * 2);
       } else {
         break;
       }
     }
-    n_coords = s.n1;
-    coords_len = chain_len;
-    prof_collect();
+    cons.n_coords = s.n1;
+    cons.coords_len = strm.log.chain_len;
+    prof.collect();
   }
   Walk walk_rounds(CoordStep& s) {
-    if (N > 32 && (wide32 || frontier_fallback)) return rounds_step32(s);
+    if (N > 32 && (strm.wide32 || frontier_fallback)) return rounds_step32(s);
     if (N > 32) return rounds_coop(s);
     if (!s.fresh && s.maxlen < 0xFFFF) return walk_online(s);
     return walk_fss(s);
@@ -1039,15 +856,15 @@ struct hge_engine {
       KLAUNCH(k_frontier_start, dim3(1), dim3(256), 0, st, t, s.olen, s.len, s_fst.p, s.fss_lo,
               (int32_t*)nullptr, (uint64_t*)nullptr, 0);
     const int64_t guess = (s.n1 - s.n0) + 16 * (int64_t)N;  // the grid loops past it
-    und_appended = dividing && n_divided == s.n0;
+    cons.und_appended = cons.dividing && cons.n_divided == s.n0;
     Walk w;
     w.assigned = true;
-    w.tail_done = n_und + (s.n1 - n_divided) <= 65536;
+    w.tail_done = cons.n_und + (s.n1 - cons.n_divided) <= 65536;
     const RoundAssign ra = round_assign(s, w.tail_done);
     KLAUNCH_AS(k.fss_name, k.fss, dim3((unsigned)std::min<int64_t>(1024, div_up(guess * k.NPC, 256))), dim3(256), 0,
                st, t, s.fss_lo, s.fss_off, 0, (int32_t*)nullptr, (uint16_t*)d_FSS.p, (const int32_t*)s.fss_total);
     KLAUNCH_AS(k.walk_name, k.walk, dim3(1), dim3(1024), 0, st, t, (const uint16_t*)d_FSS.p, s.olen, s.len, s.rstate,
-               0, R, dbg_p(), (const int32_t*)s_fst.p, ra);
+               0, cons.R, dbg_p(), (const int32_t*)s_fst.p, ra);
     return w;
   }
 
@@ -1057,7 +874,7 @@ struct hge_engine {
   Walk walk_fss(CoordStep& s) {
     const Tables t = tables();
     const WalkKernels& k = walk_kernels();
-    const int Rprev = R;  // C rows >= Rprev are empty before this batch
+    const int Rprev = cons.R;  // C rows >= Rprev are empty before this batch
     std::vector<int32_t> fst(N + 1, 0);
     if (!s.fresh) {
       s_fst.need(N + 1);
@@ -1073,7 +890,7 @@ struct hge_engine {
       for (int c = 0; c < N; c++) {
         lo_off[c] = fst[1 + c];
         lo_off[N + c] = tot;
-        tot += std::max(0, chain_len[c] - fst[1 + c]);
+        tot += std::max(0, strm.log.chain_len[c] - fst[1 + c]);
       }
       lo_off[2 * N] = tot;
       h2d(s.fss_lo, lo_off.data(), 4 * (2 * N + 1));
@@ -1093,13 +910,12 @@ struct hge_engine {
     const int32_t* resume = nw > 1 ? spec_walk(t, s, k, nw) : nullptr;
     KLAUNCH_AS(k.walk_name, k.walk, dim3(1), dim3(1024), 0, st, t, (const uint16_t*)d_FSS.p, s.olen, s.len, s.rstate,
                resume ? 0 : rlo, resume ? 0 : Rprev, dbg_p(), resume, RoundAssign{});
-    if (resume && getenv("HGE_WALK_DEBUG")) walk_debug(nw);
+    if (resume && hge_hooks::walk_debug()) walk_debug(nw);
     return {};
   }
   // the speculative walkers (hge_walk_spec.hip) and their join; returns the join's resume row
   const int32_t* spec_walk(const Tables& t, const CoordStep& s, const WalkKernels& k, int nw) {
-    const char* hc = getenv("HGE_WALK_HCAP");  // tests: force the capacity fallback
-    const int Hcap = hc ? std::max(2, atoi(hc)) : std::max(256, std::min(Rcap, 3 * (Rcap / nw) + 256));
+    const int Hcap = hge_hooks::walk_hcap(std::max(256, std::min(Rcap, 3 * (Rcap / nw) + 256)));
     if ((size_t)nw * Hcap * N > s_H.n) {
       s_H.need((size_t)nw * Hcap * N);  // epoch 0 never matches a launch's tag
       HGE_HIPCHK(hipMemsetAsync(s_H.p, 0, s_H.n * sizeof(uint64_t), st));
@@ -1125,9 +941,9 @@ struct hge_engine {
     } else if (!w.assigned) {
       // DivideRounds right after (divide()) with nothing coordinated but undivided:
       // the new ids join the undetermined list here (no k_iota launch)
-      und_appended = dividing && n_divided == s.n0;
+      cons.und_appended = cons.dividing && cons.n_divided == s.n0;
       KLAUNCH(k_round_assign, dim3(div_up(m, 256)), dim3(256), 0, st, t, (int)s.n0, (int)s.n1,
-              (const int32_t*)s.rstate, s_newwit.p, s.rstate + 2, und_appended ? d_und.p + n_und : (int32_t*)nullptr);
+              (const int32_t*)s.rstate, s_newwit.p, s.rstate + 2, cons.und_appended ? d_und.p + cons.n_und : (int32_t*)nullptr);
     }
   }
   // k_round_tail, unless the walk's block did its work: the new witnesses' see /
@@ -1139,38 +955,38 @@ struct hge_engine {
     if (w.tail_done) return 0;
     const Tables t = tables();
     const int m = (int)(s.n1 - s.n0), G = wit_group();
-    const int64_t n_mr = n_und + (s.n1 - n_divided);
+    const int64_t n_mr = cons.n_und + (s.n1 - cons.n_divided);
     const int mr = !s.fresh && n_mr <= 65536 ? (int)std::max<int64_t>(1, std::min<int64_t>(16, div_up(n_mr, 2048))) : 0;
     const int64_t wmax = std::min<int64_t>(m, (int64_t)Rcap * N);  // witnesses <= both
     const int nb_wb = std::max(1, std::min(div_up(wmax * NW * G, 256), 8192));
     KLAUNCH(k_round_tail, dim3(nb_wb + div_up(Rcap, 4) + mr), dim3(256), 0, st, t, s_newwit.p, s.rstate + 2,
             N > 32 ? (const uint64_t*)d_ssc.p : nullptr, G, nb_wb, (const int32_t*)s.rstate, d_minw.p, w.err_src, mr,
-            (const int32_t*)d_und.p, (int)n_und, (int)n_divided, (int)s.n1);
+            (const int32_t*)d_und.p, (int)cons.n_und, (int)cons.n_divided, (int)s.n1);
     if (!s.fresh && !mr) {
       int32_t* mnr = d_minw.p + Rcap + hge_plan::kTailMinRound;
-      if (n_und > 0)
-        KLAUNCH(k_min_round, dim3(div_up(n_und, 256)), dim3(256), 0, st, d_round.p, d_und.p, (int)n_und, mnr);
-      if (s.n1 > n_divided)
-        KLAUNCH(k_min_round_range, dim3(div_up(s.n1 - n_divided, 256)), dim3(256), 0, st, d_round.p,
-                (int)n_divided, (int)s.n1, mnr);
+      if (cons.n_und > 0)
+        KLAUNCH(k_min_round, dim3(div_up(cons.n_und, 256)), dim3(256), 0, st, d_round.p, d_und.p, (int)cons.n_und, mnr);
+      if (s.n1 > cons.n_divided)
+        KLAUNCH(k_min_round_range, dim3(div_up(s.n1 - cons.n_divided, 256)), dim3(256), 0, st, d_round.p,
+                (int)cons.n_divided, (int)s.n1, mnr);
     }
     return mr;
   }
   // the one readback: the rounds' first witnesses and the tail words behind them
   RoundsOutcome read_rounds(const CoordStep& s, const Walk& w, int mr) {
-    h_minw.resize(Rcap + hge_plan::kTailPartial + mr);
-    d2h(h_minw.data(), d_minw.p, 4 * h_minw.size());
+    cons.h_minw.resize(Rcap + hge_plan::kTailPartial + mr);
+    d2h(cons.h_minw.data(), d_minw.p, 4 * cons.h_minw.size());
     sync();
-    minw_full = false;  // every round's first witness is in d_minw now
-    const hge_plan::RoundsTail r = hge_plan::parse_rounds_tail(h_minw.data() + Rcap, mr);
-    if (!s.fresh) mnr_pre = r.min_round;
-    mnr_key[0] = s.fresh ? -1 : n_und;
-    mnr_key[1] = n_divided;
-    mnr_key[2] = s.n1;
+    cons.minw_full = false;  // every round's first witness is in d_minw now
+    const hge_plan::RoundsTail r = hge_plan::parse_rounds_tail(cons.h_minw.data() + Rcap, mr);
+    if (!s.fresh) cons.mnr_pre = r.min_round;
+    cons.mnr_key[0] = s.fresh ? -1 : cons.n_und;
+    cons.mnr_key[1] = cons.n_divided;
+    cons.mnr_key[2] = s.n1;
     if (w.err_src ? r.handoff_err != 0 : w.host_err) return RoundsOutcome::HandoffTimeout;
     if (r.overflow) return RoundsOutcome::Grow;
-    R = r.R;
-    h_minw.resize(R);
+    cons.R = r.R;
+    cons.h_minw.resize(cons.R);
     return RoundsOutcome::Done;
   }
 
@@ -1178,16 +994,14 @@ struct hge_engine {
   // state: one per ~192 positions of the shortest chain, up to 32 (HGE_WALKERS
   // overrides; 0 or 1 = the sequential walk).  Short graphs walk sequentially.
   int spec_walkers(int minlen) {
-    const char* ev = getenv("HGE_WALKERS");  // read per call: the tests vary it
-    const int env = ev ? atoi(ev) : -1;
+    const int env = hge_hooks::walkers();
     const int nw = env >= 0 ? env : (minlen >= 4 * 192 ? std::min(32, minlen / 192) : 0);
     return std::max(0, std::min(nw, 64));
   }
 
   // HGE_WALK_DEBUG: per-walker rows, merge results and cycle stamps on stderr
-  DBuf<uint64_t> s_wdbg;
   uint64_t* walk_dbg(int nw) {
-    if (!getenv("HGE_WALK_DEBUG")) return nullptr;
+    if (!hge_hooks::walk_debug()) return nullptr;
     s_wdbg.need(4 * (size_t)nw);
     return s_wdbg.p;
   }
@@ -1217,10 +1031,9 @@ struct hge_engine {
       HGE_HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&coop_spec_nb, coop_spec_fn(), sbs, 0));
     }
     const int cap = (int)std::min<int64_t>(16, (int64_t)coop_spec_nb * coop_ncu / N);
-    const char* ev = getenv("HGE_COOP_WALKERS");
     // above N = 128 only 2 walkers fit, and the 512-thread sequential kernel is faster
     // than 2 walkers sharing each CU (22.5 vs 33.6 ms at 256/2M, profiles/r01r_*)
-    int nw = ev ? atoi(ev) : (minlen >= 1024 && N <= 128 ? 8 : 0);
+    int nw = hge_hooks::coop_walkers(minlen >= 1024 && N <= 128 ? 8 : 0);
     nw = std::min(nw, cap);
     return nw >= 2 ? nw : 0;
   }
@@ -1239,7 +1052,6 @@ struct hge_engine {
   // other's missing workgroups, so one process runs them one at a time.  (Grids of
   // other processes on the same device are not covered: wide engines need the
   // device to themselves)
-  std::vector<std::pair<std::pair<const void*, int>, int>> resident_nb;
   hipError_t launch_resident(const void* fn, dim3 grid, dim3 block, void** args) {
     const int bs = (int)(block.x * block.y * block.z);
     int nb = -1;
@@ -1269,8 +1081,6 @@ struct hge_engine {
 
   // rounds of a wide hashgraph: the frontier start, a split run's joined rows or the speculative
   // walkers, then the walk's one grid (the caller holds frontier_lock() until the stream has drained)
-  bool frontier_fallback = false;  // k_round_step32 for good after a hand-off timeout
-  int64_t n_frontier_fallbacks = 0;
   Walk rounds_coop(CoordStep& s) {
     const Tables t = tables();
     s_fst.need(N + 1);
@@ -1287,7 +1097,7 @@ struct hge_engine {
     const int32_t* rlo_dev = s.fresh ? nullptr : s_fst.p;
     if (s.fresh) readback(&rlo, s_fst.p, 1);
     if (rlo == INF32) return {};
-    const int Rprev = R;
+    const int Rprev = cons.R;
     if (!coop_resident()) {  // a device too small for the walk's grid
       frontier_fallback = true;
       return rounds_step32(s);
@@ -1297,7 +1107,7 @@ struct hge_engine {
     if (s.maxlen >= 0xFFFF)
       throw Error(HGE_ERR_INTERNAL, "packed rounds walk reached a chain past 65,534 events");
     const bool from_zero = s.fresh && rlo == 0 && Rprev == 0;
-    if (ext_on && from_zero && install_ext_rows(s, rlo)) return {};
+    if (cons.ext_on && from_zero && install_ext_rows(s, rlo)) return {};
     Walk w;
     const int nw = from_zero && rlo == 0 ? coop_walkers(s.minlen) : 0;  // (the joined rows may have moved rlo)
     if (nw >= 2) {
@@ -1327,16 +1137,16 @@ struct hge_engine {
   // frontier rows joined from the walkers of all ranks (babble_amd/dist.py); true:
   // nothing is left to walk (rstate says why), else rlo is the row to resume from
   bool install_ext_rows(const CoordStep& s, int32_t& rlo) {
-    const int K = ext_rows;  // true rows 0 .. K-1
+    const int K = cons.ext_rows;  // true rows 0 .. K-1
     if (K + 1 >= Rcap) {  // the rounds table must hold them: overflow, grow, come back
       const int32_t ov[2] = {0, hge_plan::kRoundsFull};
       h2d(s.rstate, ov, 8);
       return true;
     }
-    ext_on = false;
-    h2d(d_C.p, ext_C.data(), sizeof(int32_t) * (size_t)K * N);
-    if (K > 1) h2d(d_ssc.p + (size_t)N * NW, ext_ssc.data() + (size_t)N * NW, sizeof(uint64_t) * (size_t)(K - 1) * N * NW);
-    if (ext_natural) {  // the walk ended: row K is the empty frontier
+    cons.ext_on = false;
+    h2d(d_C.p, cons.ext_C.data(), sizeof(int32_t) * (size_t)K * N);
+    if (K > 1) h2d(d_ssc.p + (size_t)N * NW, cons.ext_ssc.data() + (size_t)N * NW, sizeof(uint64_t) * (size_t)(K - 1) * N * NW);
+    if (cons.ext_natural) {  // the walk ended: row K is the empty frontier
       const int32_t rs0 = K;
       h2d(s.rstate, &rs0, 4);
       return true;
@@ -1351,9 +1161,7 @@ struct hge_engine {
     const int32_t* olen = s.olen;
     const int32_t* len = s.len;
     int32_t* err = s_bar.p + 1;
-    const char* hc = getenv("HGE_WALK_HCAP");  // tests: force the capacity fallback
-    const int Hcap = hc ? std::max(2, std::min(0xFFFF, atoi(hc)))
-                        : std::min(0xFFFF, std::min(Rcap, std::max(256, 3 * (Rcap / nw) + 256)));
+    const int Hcap = std::min(0xFFFF, hge_hooks::walk_hcap(std::min(Rcap, std::max(256, 3 * (Rcap / nw) + 256))));
     int TS = 64;
     while (TS < 2 * Hcap) TS <<= 1;
     const size_t nh = (size_t)nw * Hcap * N, nt = (size_t)nw * TS;
@@ -1374,16 +1182,16 @@ struct hge_engine {
     s_cn.need(2 * (size_t)nw + 1);
     HGE_HIPCHK(hipMemsetAsync(s_cM.p, 0xFF, (size_t)nw * sizeof(uint64_t), st));
     int64_t nev = 0;
-    for (int c = 0; c < N; c++) nev += chain_len[c];
+    for (int c = 0; c < N; c++) nev += strm.log.chain_len[c];
     // guesses (measured over seeds 1-3, profiles/r01/guess128): time cuts at N <= 64,
     // alternating length/time cuts above
     const int guess = N <= 64 ? 1 : 2;
     CoopSpec cs{s_cH.p, s_cS.p, s_cT.p, (unsigned long long*)s_cM.p, s_cn.p, nw, Hcap, TS,
                 coop_epoch, nev, guess};
     void* sargs[] = {&t, &FDT, &olen, &len, &cs, &err};
-    prof_begin("k_rounds_coop_spec");
+    prof.begin("k_rounds_coop_spec");
     HGE_HIPCHK(launch_resident(coop_spec_fn(), dim3(nw * N), dim3(coop_spec_bs), sargs));
-    prof_end();
+    prof.end();
     int32_t* resume = s_cn.p + 2 * nw;
     KLAUNCH(k_coop_join, dim3(64), dim3(256), 0, st, t, cs, d_ssc.p, s.rstate, resume);
     int32_t hres[2] = {0, 0};
@@ -1395,7 +1203,7 @@ struct hge_engine {
       return -1;
     }
     readback(&hres[1], resume, 1);
-    if (getenv("HGE_WALK_DEBUG")) {
+    if (hge_hooks::walk_debug()) {
       std::vector<int32_t> hn(2 * nw);
       std::vector<uint64_t> mg(nw);
       readback(hn.data(), s_cn.p, hn.size());
@@ -1427,25 +1235,23 @@ struct hge_engine {
       int32_t* nohist = nullptr;
       int hmax = 0, extra = 0;
       // tests: the walk stalls at this hand-off epoch (chain 0 never publishes it)
-      const char* hs = getenv("HGE_TEST_HANDOFF_STALL");
-      int stall_ep = hs ? atoi(hs) : 0;
+      int stall_ep = hge_hooks::test_handoff_stall();
       int force_exact = walk_force_exact();
       // tests: at this hand-off epoch chain 1 flags its staged member row (a fine one)
-      const char* mf = getenv("HGE_TEST_DIR_MEMBER_FLAG");
-      int mflag_ep = mf ? atoi(mf) : 0;
+      int mflag_ep = hge_hooks::test_dir_member_flag();
       void* dargs[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
                        &nostart, &nohist, &hmax, &nostart, &extra, &stall_ep, &force_exact, &mflag_ep, &paths,
                        &paths_next};
-      prof_begin("k_rounds_direct");
+      prof.begin("k_rounds_direct");
       HGE_HIPCHK(launch_resident(direct_fn(), dim3(N), dim3(1024), dargs));
-      prof_end();
+      prof.end();
     } else {
       void* args[] = {&t, &FDT, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &dbg};
-      prof_begin("k_rounds_coop");
+      prof.begin("k_rounds_coop");
       HGE_HIPCHK(launch_resident((const void*)k_rounds_coop, dim3(N), dim3(COOP_BS), args));
-      prof_end();
+      prof.end();
     }
-    if (getenv("HGE_TEST_HANDOFF_FAIL")) {  // tests: the walk reports a hand-off timeout
+    if (hge_hooks::test_handoff_fail()) {  // tests: the walk reports a hand-off timeout
       const int32_t one = 1, down = hge_plan::kRoundsStoodDown;
       h2d(err, &one, 4);
       h2d(rstate + 1, &down, 4);
@@ -1461,8 +1267,6 @@ struct hge_engine {
   // cleared once here.  Walk k adds to slot k & 1 and clears the other slot as it ends,
   // for the walk after it on the stream: no clearing launch per walk (an online call is a
   // few hundred microseconds, a memset node was ~10 of them).
-  DBuf<unsigned long long> s_wpaths;
-  int walk_seq = 0;
   unsigned long long* walk_paths() {
     if (!s_wpaths.p) {
       s_wpaths.need(4);
@@ -1474,9 +1278,6 @@ struct hge_engine {
   // The order stage's sort-path counters (hge_sort_paths): two slots of {packed, index,
   // k_bucket_sort_big's next bucket, unused}, handed over like the walk's.  An order stage without a bucket past 512 keys launches
   // no counting kernel and reports (0, 0).
-  DBuf<unsigned long long> s_spaths;
-  int sort_seq = 0;
-  bool sort_counted = false;
   SortCtl sort_ctl() {
     if (!s_spaths.p) {
       s_spaths.need(8);
@@ -1486,15 +1287,11 @@ struct hge_engine {
     }
     sort_seq++;
     sort_counted = true;
-    const char* e = getenv("HGE_TEST_SORT_INDEX");  // tests: every bucket takes the index sort
     return SortCtl{s_spaths.p + 4 * (sort_seq & 1), s_spaths.p + 4 * ((sort_seq + 1) & 1),
-                   e && atoi(e) != 0 ? 1 : 0};
+                   hge_hooks::test_sort_index()};
   }
   // tests (HGE_TEST_DIR_EXACT=1): every round of the walk takes the 16-bit select
-  static int walk_force_exact() {
-    const char* e = getenv("HGE_TEST_DIR_EXACT");
-    return e && atoi(e) != 0 ? 1 : 0;
-  }
+  static int walk_force_exact() { return hge_hooks::test_dir_exact(); }
   const void* direct_fn() const {
     return N <= 64 ? (const void*)k_rounds_direct<1024, 64>
          : N <= 128 ? (const void*)k_rounds_direct<1024, 128>
@@ -1504,9 +1301,9 @@ struct hge_engine {
   // N > 32: lastAncestors live in the packed 16-bit table while every chain holds at
   // most 65,534 events; a longer chain switches the engine to int32 LA rows for good
   // (to_wide32 below), which the N <= 32 path uses from the start
-  bool sweep16() const { return N > 32 && !wide32; }
+  bool sweep16() const { return N > 32 && !strm.wide32; }
   // the median's threshold rows as uint16 (k_witness_la, k_median_wave's 4-witness lanes)
-  bool wla16() const { return N > 192 && (N & 3) == 0 && !wide32; }
+  bool wla16() const { return N > 192 && (N & 3) == 0 && !strm.wide32; }
 
   // the switch to int32 positions (hge_wide32.hip): the int32 LA rows of every event
   // with coordinates, unpacked from LA16; from here on the N <= 32 sweeps and
@@ -1526,17 +1323,17 @@ struct hge_engine {
       }
     };
     ensure_fdtd();  // (the pass reads the uint16 runs)
-    if (!(w32_done & 4)) {
+    if (!(strm.w32_done & 4)) {
       const size_t n = (size_t)N * ccap * N;  // [N][ccap][N], written by k_la16_to_la32 below
       d_LA.regrow_rows(0, 0, 0, sizeof(int32_t) * n, n, false, st);
       sync();
-      w32_done |= 4;
+      strm.w32_done |= 4;
       test_stop(1);
     }
     if (fdt16()) {  // the runs and FD rows continue in int32 from here: widen the kept ones
       const size_t n = (size_t)N * N * ccap;
       for (int which = 0; which < 2; which++) {
-        if (w32_done & (1 << which)) continue;
+        if (strm.w32_done & (1 << which)) continue;
         DBuf<int32_t>& b = which ? d_FD : d_FDT;
         DBuf<int32_t> q;
         q.need(n);
@@ -1544,18 +1341,18 @@ struct hge_engine {
                 (const uint16_t*)b.p, q.p, n, which);
         sync();
         b.adopt(std::move(q));
-        w32_done |= 1 << which;
+        strm.w32_done |= 1 << which;
         test_stop(2 + which);
       }
     }
     s_w32.need(N);
-    h2d(s_w32.p, coords_len.data(), 4 * (size_t)N);
-    wide32 = true;
-    wide32_pending = false;
-    w32_done = 0;
+    h2d(s_w32.p, cons.coords_len.data(), 4 * (size_t)N);
+    strm.wide32 = true;
+    strm.wide32_pending = false;
+    strm.w32_done = 0;
     Tables t = tables();
     int64_t most = 1;
-    for (int c = 0; c < N; c++) most = std::max<int64_t>(most, (int64_t)coords_len[c] * N);
+    for (int c = 0; c < N; c++) most = std::max<int64_t>(most, (int64_t)cons.coords_len[c] * N);
     KLAUNCH(k_la16_to_la32, dim3((unsigned)std::min<int64_t>(div_up(most, 256), 4096), N), dim3(256), 0, st, t,
             (const uint32_t*)d_LA16.p, (const int32_t*)s_w32.p);
   }
@@ -1570,7 +1367,7 @@ struct hge_engine {
     int32_t rlo = INF32;
     readback(&rlo, s_fst.p, 1);
     if (rlo == INF32) return {};
-    const int Rprev = R, NB = 32;
+    const int Rprev = cons.R, NB = 32;
     s_w32a.need(NB);
     for (int r = rlo;;) {
       HGE_HIPCHK(hipMemsetAsync(s_w32a.p, 0, 4 * NB, st));
@@ -1582,13 +1379,13 @@ struct hge_engine {
       readback(alive.data(), s_w32a.p, NB);
       for (int q = 0; q < k; q++)
         if (!alive[q]) {  // row r + q + 1 is empty: the rounds end there
-          const int32_t rs[2] = {std::max(R, r + q + 1), 0};
+          const int32_t rs[2] = {std::max(cons.R, r + q + 1), 0};
           h2d(s.rstate, rs, 8);
           return {};
         }
       r += k;
       if (k < NB) {  // the rounds table is full: grown by the caller, walked again
-        const int32_t rs[2] = {R, hge_plan::kRoundsFull};
+        const int32_t rs[2] = {cons.R, hge_plan::kRoundsFull};
         h2d(s.rstate, rs, 8);
         return {};
       }
@@ -1599,11 +1396,11 @@ struct hge_engine {
   // k_fd_transpose_ts<uint16_t>: half the run table's bytes written and read).  Neither the
   // direct walk nor theta reads FDT; the speculative walkers (N <= 128) and the
   // FDT-gather walk (N % 4 != 0) read int32 runs.
-  bool fdt16() const { return N > 128 && (N & 3) == 0 && !wide32; }
+  bool fdt16() const { return N > 128 && (N & 3) == 0 && !strm.wide32; }
 
   // 32 < N <= 256: lastAncestors by windowed exact propagation (hge_coords_win.hip)
   // instead of the sweeps
-  bool la_windows() const { return N > 32 && N <= 256 && !wide32; }
+  bool la_windows() const { return N > 32 && N <= 256 && !strm.wide32; }
 
   // passes over windows of the new ids until one changes no row (n_sweeps = passes
   // run); one window is exact in its first pass (its starting rows are final)
@@ -1618,7 +1415,7 @@ struct hge_engine {
     const int64_t WMIN = 4096;  // ids per window at least
     const int per_cu = npow == 256 ? 1 : 2;
     int64_t G = std::min<int64_t>((int64_t)n_cu() * per_cu, std::max<int64_t>(1, ne / WMIN));
-    if (const char* g = getenv("HGE_LW_G")) G = std::max(1, atoi(g));
+    G = hge_hooks::lw_windows(G);
     int64_t WN = (div_up(ne, G) + LW_K - 1) / LW_K * LW_K;
     G = div_up(ne, WN);
     s_lwplan.need(ne);
@@ -1670,7 +1467,7 @@ struct hge_engine {
 
   // the one-pass lastAncestors kernel (k_la_seq) takes batches of m new events at N <= 32
   bool la_seq_ok(int64_t m) const {
-    return !sweep16() && N <= 32 && m > 0 && m * (N <= 16 ? 16 : 32) <= LASEQ_MAX && !getenv("HGE_NO_LASEQ");
+    return !sweep16() && N <= 32 && m > 0 && m * (N <= 16 ? 16 : 32) <= LASEQ_MAX && !hge_hooks::no_laseq();
   }
   // lastAncestors of the new events: windows, one pass, or sweeps to the fixed point
   static constexpr int MAXSW = 4096;  // sweeps at most
@@ -1690,7 +1487,7 @@ struct hge_engine {
     // past a fresh state: + k_fd_qlo's N blocks, + k_frontier_start's block when coords_b walks as an online
     // call; at N <= 16 the batch's firstDescendants in the same launch instead (no runs, transpose, k_fd_qlo)
     const bool q = !s.fresh, fst = q && s.maxlen < 0xFFFF;
-    const bool fd = q && N <= 16 && !getenv("HGE_NO_FD_DIRECT");
+    const bool fd = q && N <= 16 && !hge_hooks::no_fd_direct();
     if (fst) s_fst.need(N + 1);
     int32_t* fp = fst ? s_fst.p : (int32_t*)nullptr;
     int32_t* fl = fst ? s.fss_lo : (int32_t*)nullptr;
@@ -1780,11 +1577,11 @@ struct hge_engine {
   }
   // every reader of d_FDTD / d_FDTW: the whole table, when a bulk replay left it stale
   void ensure_fdtd() {
-    if (!fdtd_stale) return;
+    if (!cons.fdtd_stale) return;
     if (!fdt16()) throw Error(HGE_ERR_INTERNAL, "stale FD timestamp rows past the uint16 runs");
     HGE_HIPCHK(hipMemsetAsync(s_fdlo.p, 0, 4 * (size_t)N, st));
-    fdtd_pass("fdtd_ensure (k_fd_transpose_ts<uint16_t>)", div_up(std::max(fdtd_maxlen, 1), 64));
-    fdtd_stale = false;
+    fdtd_pass("fdtd_ensure (k_fd_transpose_ts<uint16_t>)", div_up(std::max(cons.fdtd_maxlen, 1), 64));
+    cons.fdtd_stale = false;
   }
   // firstDescendants: the FDT runs from the LA rows, then FDT -> FD rows
   void first_descendants(const Tables& t, const CoordStep& s) {
@@ -1819,15 +1616,15 @@ struct hge_engine {
       span = std::max(span, s.maxlen);
     }
     // (a split part writes the timestamp rows of its own candidates only)
-    if (s.fresh) fdtd_stale = false;  // (every row is written again below, or marked)
+    if (s.fresh) cons.fdtd_stale = false;  // (every row is written again below, or marked)
     if (s.fd_rows_only) {
       // the FD rows alone: the timestamp table is stale from position 0 of every chain
       KLAUNCH(k_fd_rows16, dim3(N, div_up(N, 64), std::min(div_up(span, 64), 65535)), dim3(256), 0, st, t,
               (const uint16_t*)d_FDT.p, (const int32_t*)s.qlo, len);
       s_fdlo.need(2 * (size_t)N);
-      h2d(s_fdlo.p + N, chain_len.data(), 4 * (size_t)N);
-      fdtd_maxlen = s.maxlen;
-      fdtd_stale = true;
+      h2d(s_fdlo.p + N, strm.log.chain_len.data(), 4 * (size_t)N);
+      cons.fdtd_maxlen = s.maxlen;
+      cons.fdtd_stale = true;
     } else if (fdt16())
       KLAUNCH((k_fd_transpose_ts<uint16_t>), dim3(N, div_up(N, 64), std::min(div_up(span, 64), 65535)), dim3(256),
               0, st, t, (const uint16_t*)d_FDT.p, s.qlo, len, (const int32_t*)s.cand_lo,
@@ -1896,20 +1693,20 @@ struct hge_engine {
   unsigned long long* out_tx(const Batch& b) const { return (unsigned long long*)(s_out.p + b.out.o_tx); }
   int32_t* out_word(size_t k) const { return s_out.p + k; }
   // the new LastConsensusRound for the results header, when the device holds it
-  const int32_t* lcr_src(const Batch& b) const { return b.lcr_dev ? (const int32_t*)(c_flags + 1) : nullptr; }
+  const int32_t* lcr_src(const Batch& b) const { return b.lcr_dev ? (const int32_t*)(cons.c_flags + 1) : nullptr; }
   void out_init(const Batch& b) {
     const int nh = (int)b.out.header();
     KLAUNCH(k_out_init, dim3(div_up(nh, 256)), dim3(256), 0, st, s_out.p, nh, lcr_src(b));
   }
   // the control block's regions in s_cctl (host-built, or k_consensus_dyn's to fill)
   void bind_ctl(const hge_plan::CtlLayout& L) {
-    c_nc = (int64_t*)s_cctl.p;
-    c_Rc = s_cctl.p + L.Rc;
-    c_Lc = s_cctl.p + L.Lc;
-    c_flags = s_cctl.p + L.flags;
-    c_pr = s_cctl.p + L.pr;
-    c_pidx = s_cctl.p + L.pidx;
-    c_sgo = s_cctl.p + L.sgo;
+    cons.c_nc = (int64_t*)s_cctl.p;
+    cons.c_Rc = s_cctl.p + L.Rc;
+    cons.c_Lc = s_cctl.p + L.Lc;
+    cons.c_flags = s_cctl.p + L.flags;
+    cons.c_pr = s_cctl.p + L.pr;
+    cons.c_pidx = s_cctl.p + L.pidx;
+    cons.c_sgo = s_cctl.p + L.sgo;
   }
 
   void consensus_batch(const std::vector<int64_t>& calls, bool do_fame, bool do_order, bool commit,
@@ -1947,8 +1744,8 @@ struct hge_engine {
     tp[3] = now_ns();
     close_batch(b);
     tp[4] = now_ns();
-    if (b.ncalls > 1000 && getenv("HGE_HOST_PHASES")) phases_line(tp);
-    prof_collect();
+    if (b.ncalls > 1000 && hge_hooks::host_phases()) phases_line(tp);
+    prof.collect();
   }
   void phases_line(const int64_t* tp) const {
     fprintf(stderr, "[hge consensus] prologue %.3f ms, fame %.3f ms (incl. syncs), order enqueue %.3f ms, closing %.3f ms\n",
@@ -1958,26 +1755,26 @@ struct hge_engine {
   // R_c, the candidates and their lowest round, the order pass's rounds, the results layout
   void prologue(Batch& b, const std::vector<int64_t>& calls) {
     consensus_sync();  // (the results block is reused below)
-    x_iter = 0;
-    b.Rc = hge_plan::rounds_at_calls(calls, h_minw);
-    b.fresh_und = und_fresh;
-    und_fresh = false;
-    b.ord = b.do_order && n_und > 0;
-    b.ncand = (int)n_und;
+    cons.x_iter = 0;
+    b.Rc = hge_plan::rounds_at_calls(calls, cons.h_minw);
+    b.fresh_und = cons.und_fresh;
+    cons.und_fresh = false;
+    b.ord = b.do_order && cons.n_und > 0;
+    b.ncand = (int)cons.n_und;
     b.cand = d_und.p;
     // a split part's candidates: the events [cand_lo, its end) of the fresh list (identity)
     b.spl = split_on() && b.ord && b.fresh_und;
     if (b.spl) {
-      b.cand = d_und.p + sp.clo[sp.part];
-      b.ncand = (int)(sp.a[sp.part + 1] - sp.clo[sp.part]);
+      b.cand = d_und.p + strm.sp.clo[strm.sp.part];
+      b.ncand = (int)(strm.sp.a[strm.sp.part + 1] - strm.sp.clo[strm.sp.part]);
     }
     // lowest candidate round (a fresh replay's candidates include event 0, round 0)
     int32_t mnr = 0;
-    const bool pre = mnr_key[0] >= 0 && !b.spl && n_divided == mnr_key[2] &&
-                     n_und == mnr_key[0] + (mnr_key[2] - mnr_key[1]);
-    mnr_key[0] = -1;
+    const bool pre = cons.mnr_key[0] >= 0 && !b.spl && cons.n_divided == cons.mnr_key[2] &&
+                     cons.n_und == cons.mnr_key[0] + (cons.mnr_key[2] - cons.mnr_key[1]);
+    cons.mnr_key[0] = -1;
     if (b.ord && !b.fresh_und && pre) {
-      mnr = mnr_pre;
+      mnr = cons.mnr_pre;
     } else if (b.ord && (!b.fresh_und || b.spl)) {
       h2d(s_small.p + 7, &kInf, 4);
       KLAUNCH(k_min_round, dim3(div_up(b.ncand, 256)), dim3(256), 0, st, d_round.p, b.cand, b.ncand,
@@ -1986,7 +1783,7 @@ struct hge_engine {
     }
     b.rr_lo = mnr + 1;
     // a split part's calls end at its last one: later rounds receive nothing it commits
-    b.R_last = b.spl ? b.Rc[sp.cb[sp.part + 1] - 1] : b.Rc[b.ncalls - 1];
+    b.R_last = b.spl ? b.Rc[strm.sp.cb[strm.sp.part + 1] - 1] : b.Rc[b.ncalls - 1];
     b.nr = b.ord ? std::max(0, b.R_last - b.rr_lo) : 0;
     // the results block's size is known before DecideFame: the single-call fame kernel
     // writes its header
@@ -1996,22 +1793,22 @@ struct hge_engine {
   FameCall fame_call_args(const Batch& b, int32_t* hdr) const {
     const int nrounds = b.w.nrounds();
     FameCall f{};
-    f.pr_round = c_pr;
-    f.pr_off = c_pr + nrounds;
-    f.pr_cf = c_pr + 2 * nrounds;
-    f.pr_len = c_pr + 3 * nrounds;
+    f.pr_round = cons.c_pr;
+    f.pr_off = cons.c_pr + nrounds;
+    f.pr_cf = cons.c_pr + 2 * nrounds;
+    f.pr_len = cons.c_pr + 3 * nrounds;
     f.nrounds = nrounds;
     f.npairs = b.w.npairs;
-    f.nc = c_nc;
-    f.Rc = c_Rc;
+    f.nc = cons.c_nc;
+    f.Rc = cons.c_Rc;
     f.dec = s_dec.p;
     f.decbit = s_decbit.p;
-    f.Lc = c_Lc;
+    f.Lc = cons.c_Lc;
     f.ncalls = b.ncalls;
-    f.lcr_start = lcr;
+    f.lcr_start = cons.lcr;
     f.LCR = s_LCR.p;
     f.clast = s_clast.p;
-    f.flags = c_flags;
+    f.flags = cons.c_flags;
     f.out = hdr;
     f.nout = (int)b.out.header();
     return f;
@@ -2038,7 +1835,7 @@ struct hge_engine {
   void decide_fame(Batch& b) {
     const Tables t = tables();
     const int ncalls = b.ncalls;
-    b.lcr_new = lcr;
+    b.lcr_new = cons.lcr;
     const bool selective = b.do_fame && N % 64 == 0 && N >= 192 && !split_on() && !rec_on && ncalls > 1;
     std::vector<int> spec_r;
     hge_plan::FameWindows old;  // a widening pass: the layout it widens
@@ -2048,8 +1845,8 @@ struct hge_engine {
       // reset on the device (k_dec_relayout)
       const bool widening = selective && iter > 0;
       if (!b.do_fame) b.w = hge_plan::FameWindows();
-      else if (widening) b.w = hge_plan::plan_fame_windows(b.Rc, lcr, spec_r);
-      else b.w = hge_plan::plan_fame_windows(b.Rc, lcr, SPEC);
+      else if (widening) b.w = hge_plan::plan_fame_windows(b.Rc, cons.lcr, spec_r);
+      else b.w = hge_plan::plan_fame_windows(b.Rc, cons.lcr, SPEC);
       if (selective && iter == 0) spec_r.assign(b.w.nrounds(), SPEC);
       const hge_plan::FameWindows& w = b.w;
       const int nrounds = w.nrounds(), npairs = w.npairs;
@@ -2081,7 +1878,7 @@ struct hge_engine {
         const FameCall fc = fame_call_args(b, s_out.p);
         KLAUNCH_NW(NW, NW_PATC, k_fame_call, 64, false, dim3(1), dim3(1024), 0, st, t, fc);
         b.hdr_done = true;
-        x_iter++;
+        cons.x_iter++;
         b.lcr_dev = true;
         break;
       }
@@ -2097,7 +1894,7 @@ struct hge_engine {
           b.fame_pending.reset();
         }
         b.hdr_done = true;
-        x_iter++;
+        cons.x_iter++;
         b.lcr_dev = true;
         break;
       }
@@ -2112,10 +1909,10 @@ struct hge_engine {
         rec_dec.emplace_back((size_t)npairs * N);
         readback(rec_dec.back().data(), s_dec.p, (size_t)npairs * N);
       }
-      x_iter++;
+      cons.x_iter++;
       s_rfail.need(nrounds);
-      KLAUNCH(k_lcr_scan, dim3(1), dim3(1024), 0, st, c_Lc, ncalls, lcr, s_LCR.p, c_pr,
-              c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, s_clast.p, c_flags,
+      KLAUNCH(k_lcr_scan, dim3(1), dim3(1024), 0, st, cons.c_Lc, ncalls, cons.lcr, s_LCR.p, cons.c_pr,
+              cons.c_pr + 2 * nrounds, cons.c_pr + 3 * nrounds, nrounds, s_clast.p, cons.c_flags,
               selective ? s_rfail.p : (int32_t*)nullptr);
       if (full) {
         b.lcr_dev = true;
@@ -2124,7 +1921,7 @@ struct hge_engine {
       int32_t fl[3];
       std::vector<int32_t> rf(selective ? nrounds : 0);
       if (selective) d2h(rf.data(), s_rfail.p, 4 * (size_t)nrounds);
-      readback(fl, c_flags, 3);
+      readback(fl, cons.c_flags, 3);
       if (fl[0]) {  // a round stayed undecided past its window: widen (those rounds only)
         if (selective) {
           for (int k = 0; k < nrounds; k++)
@@ -2134,7 +1931,7 @@ struct hge_engine {
         continue;
       }
       b.lcr_new = fl[1];
-      if (b.lcr_new > lcr) b.c_set = fl[2];
+      if (b.lcr_new > cons.lcr) b.c_set = fl[2];
       break;
     }
   }
@@ -2154,12 +1951,12 @@ struct hge_engine {
     h2d(s_relay.p, rel.data(), 4 * rel.size());
     if (!plist.empty()) h2d(s_relay.p + rel.size(), plist.data(), 4 * plist.size());
     KLAUNCH(k_dec_relayout, dim3(nrounds), dim3(256), 0, st, (const uint8_t*)s_dec.p, s_dec2.p,
-            (const int32_t*)s_relay.p, (const int32_t*)(s_relay.p + nrounds), (const int32_t*)(c_pr + nrounds),
-            N, c_Lc, ncalls, c_flags);
+            (const int32_t*)s_relay.p, (const int32_t*)(s_relay.p + nrounds), (const int32_t*)(cons.c_pr + nrounds),
+            N, cons.c_Lc, ncalls, cons.c_flags);
     std::swap(s_dec, s_dec2);
     if (!plist.empty())
-      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3((unsigned)plist.size()), dim3(N), 0, st, t, c_pr,
-                 c_pr + nrounds, c_pr + 2 * nrounds, nrounds, 0, w.npairs, c_nc, c_Rc, s_dec.p,
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3((unsigned)plist.size()), dim3(N), 0, st, t, cons.c_pr,
+                 cons.c_pr + nrounds, cons.c_pr + 2 * nrounds, nrounds, 0, w.npairs, cons.c_nc, cons.c_Rc, s_dec.p,
                  (const int32_t*)(s_relay.p + rel.size()));
   }
 
@@ -2181,7 +1978,7 @@ struct hge_engine {
     oc.si = b.si;
     oc.rr_lo = b.rr_lo;
     oc.nr = b.nr;
-    oc.segoff = c_sgo;
+    oc.segoff = cons.c_sgo;
     oc.segcnt = s_segcnt.p;
     oc.seg_call = s_segcall.p;
     oc.seg_round = s_seground.p;
@@ -2210,15 +2007,15 @@ struct hge_engine {
     oc.ntx = out_tx(b);
     oc.ntxb = b.out.ntxb;
     oc.ids = out_ids(b);
-    oc.pr = c_pr;
+    oc.pr = cons.c_pr;
     oc.nrounds = b.do_fame ? b.w.nrounds() : 0;
     oc.clast = s_clast.p;
     oc.dec = s_dec.p;
-    oc.nc = c_nc;
-    oc.flags = c_flags;
-    oc.lcr_old = lcr;
-    oc.n_lo = (int)std::min<int64_t>(b.calls[0], n_coords);
-    oc.n1 = (int)n_coords;
+    oc.nc = cons.c_nc;
+    oc.flags = cons.c_flags;
+    oc.lcr_old = cons.lcr;
+    oc.n_lo = (int)std::min<int64_t>(b.calls[0], cons.n_coords);
+    oc.n1 = (int)cons.n_coords;
     oc.lcre_out = out_word(hge_plan::ResultsLayout::kLcrEvents);
     oc.front = front;
     oc.sort = sort_ctl();
@@ -2231,7 +2028,7 @@ struct hge_engine {
     if (b.wla_done || N <= 16 || b.R_last <= b.rr_lo) return;
     b.wla_done = true;
     d_WLA.need((size_t)Rcap * N * N);
-    if (N > 64 && !wide32) d_WLR.need((size_t)Rcap * N * N);
+    if (N > 64 && !strm.wide32) d_WLR.need((size_t)Rcap * N * N);
     const Tables tw = tables();
     KLAUNCH(k_witness_la, dim3(div_up(N, 64), div_up(N, 64), b.R_last - b.rr_lo), dim3(256), 0, st, tw, b.rr_lo);
   }
@@ -2246,9 +2043,9 @@ struct hge_engine {
     // (k_order_call: segments, round received with its median, the call's bucket, the
     // undetermined list, keys, the sort, the persisted fame), with DecideFame's block
     // in front when it waited (k_consensus_call)
-    const bool ocall = nr > 0 && ncalls == 1 && b.calls[0] >= n_coords && b.commit && N <= 16 && !b.spl &&
+    const bool ocall = nr > 0 && ncalls == 1 && b.calls[0] >= cons.n_coords && b.commit && N <= 16 && !b.spl &&
                        ncand <= SCAN_LDS && (int64_t)nr * group_lanes() <= 65536 && (nrounds == 0 || b.lcr_dev) &&
-                       !getenv("HGE_NO_ORDER_CALL");
+                       !hge_hooks::no_order_call();
     if (!ocall) launch_pending_fame(b);
     if (nr == 0) {
       // the results header zeroed, with the new LastConsensusRound when the device holds
@@ -2259,11 +2056,11 @@ struct hge_engine {
       return;
     }
     SegInfo& si = b.si;
-    si.pr_index = c_pidx;
+    si.pr_index = cons.c_pidx;
     if (nrounds > 0) {
-      si.pr_off = c_pr + nrounds;
-      si.pr_cf = c_pr + 2 * nrounds;
-      si.pr_len = c_pr + 3 * nrounds;
+      si.pr_off = cons.c_pr + nrounds;
+      si.pr_cf = cons.c_pr + 2 * nrounds;
+      si.pr_len = cons.c_pr + 3 * nrounds;
       si.clast = s_clast.p;
       si.dec = s_dec.p;
     }
@@ -2271,16 +2068,16 @@ struct hge_engine {
     // first call at which each event is visible (arrivals, round received); one call
     // that sees every event (an online call) needs no table: 0 for all, and the
     // header is zeroed alone (a table of every event per call grew with the stream)
-    vis_all = ncalls == 1 && b.calls[0] >= n_coords;
-    if (vis_all) {
+    cons.vis_all = ncalls == 1 && b.calls[0] >= cons.n_coords;
+    if (cons.vis_all) {
       if (!b.hdr_done) out_init(b);
     } else {  // (the header's zeroing folded into k_visibility's launch)
       const int nh = (int)b.out.header();
-      s_vis.need(std::max<int64_t>(n_coords, 1));
-      KLAUNCH(k_visibility, dim3(div_up(n_coords, 256) + div_up(nh, 256)), dim3(256), 0, st,
-              (const int64_t*)c_nc, ncalls, (int)n_coords, s_vis.p, s_out.p, nh, lcr_src(b));
+      s_vis.need(std::max<int64_t>(cons.n_coords, 1));
+      KLAUNCH(k_visibility, dim3(div_up(cons.n_coords, 256) + div_up(nh, 256)), dim3(256), 0, st,
+              (const int64_t*)cons.c_nc, ncalls, (int)cons.n_coords, s_vis.p, s_out.p, nh, lcr_src(b));
     }
-    const int32_t* visp = vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p;
+    const int32_t* visp = cons.vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p;
     // one pass into per-round capacity slots (no count round trip); theta inline
     // for N <= 64, by k_seg_theta_wide past it
     const size_t ns = (size_t)std::max<int64_t>(b.nslot, 1);
@@ -2289,7 +2086,7 @@ struct hge_engine {
     s_segdec.need(ns);
     s_segfws.need(ns * NW);
     s_theta.need(ns * N);
-    segoff_p = c_sgo;
+    cons.segoff_p = cons.c_sgo;
     if (ocall) {
       const OrderCall oc = order_call(b, 1);
       if (b.fame_pending) {
@@ -2301,14 +2098,14 @@ struct hge_engine {
       std::swap(d_und, s_und2);
       b.got_order = true;
       b.order_ran = OrderRan::CallFront;
-      if (getenv("HGE_SEG_DEBUG")) seg_debug(b);
+      if (hge_hooks::seg_debug()) seg_debug(b);
       return;
     }
     ensure_wla(b);
     const Tables t = tables();
     const int G = group_lanes();
     const dim3 sgrid(div_up((int64_t)nr * G, 256));
-    const int32_t* sgo = c_sgo;
+    const int32_t* sgo = cons.c_sgo;
     if (G == 16) {
       KLAUNCH((k_segments_1p<16, 1>), sgrid, dim3(256), 0, st, t, b.rr_lo, nr, ncalls, visp, si, sgo, s_segcnt.p,
               s_segcall.p, s_seground.p, s_segdec.p, s_segfws.p, s_theta.p);
@@ -2319,16 +2116,16 @@ struct hge_engine {
       KLAUNCH_NW(NW, NW_PAT, k_segments_1p, 64, sgrid, dim3(256), 0, st, t, b.rr_lo, nr, ncalls, visp, si, sgo,
                  s_segcnt.p, s_segcall.p, s_seground.p, s_segdec.p, s_segfws.p, s_theta.p);
     }
-    if (NW > 1 && wide32) {
+    if (NW > 1 && strm.wide32) {
       KLAUNCH_NW2(NW, NW_T, k_seg_theta32, dim3(std::min(nr, 4096)), dim3(256), 0, st, t,
-                  (const int32_t*)s_seground.p, (const int32_t*)c_sgo, (const int32_t*)s_segcnt.p, nr,
+                  (const int32_t*)s_seground.p, (const int32_t*)cons.c_sgo, (const int32_t*)s_segcnt.p, nr,
                   (const uint64_t*)s_segfws.p, s_theta.p);
     } else if (NW > 1) {
       KLAUNCH_NW2(NW, NW_T, k_seg_theta_wide, dim3(std::min(nr, 4096), nr < 64 ? 8 : 2), dim3(1024), 0, st, t,
-                  (const int32_t*)s_seground.p, (const int32_t*)c_sgo, (const int32_t*)s_segcnt.p, nr,
+                  (const int32_t*)s_seground.p, (const int32_t*)cons.c_sgo, (const int32_t*)s_segcnt.p, nr,
                   (const uint64_t*)s_segfws.p, s_theta.p, dbg_p());
     }
-    if (getenv("HGE_SEG_DEBUG")) seg_debug(b);
+    if (hge_hooks::seg_debug()) seg_debug(b);
     // round-received per candidate
     s_recv.need(ncand);
     s_rr.need(ncand);
@@ -2364,15 +2161,15 @@ struct hge_engine {
     int32_t* const cand = b.cand;
     const Tables t = tables();
     if (b.spl) {  // keep what this part's calls receive (k_split_filter)
-      const int p = sp.part;
-      const int32_t guard = p + 1 < sp.nparts ? (int32_t)sp.clo[p + 1] : INT32_MIN;
+      const int p = strm.sp.part;
+      const int32_t guard = p + 1 < strm.sp.nparts ? (int32_t)strm.sp.clo[p + 1] : INT32_MIN;
       HGE_HIPCHK(hipMemsetAsync(s_small.p + 8, 0, 4, st));
       KLAUNCH(k_split_filter, dim3(div_up(ncand, 256)), dim3(256), 0, st, (const int32_t*)cand, ncand,
-              s_recv.p, sp.cb[p], sp.cb[p + 1] - 1, guard, s_small.p + 8);
+              s_recv.p, strm.sp.cb[p], strm.sp.cb[p + 1] - 1, guard, s_small.p + 8);
     }
     if (b.order_ran == OrderRan::CallFront) return;
     const bool tail_ok = b.commit && ncalls == 1 && !b.spl && ncand <= SCAN_LDS &&
-                         (!b.do_fame || b.w.nrounds() == 0 || b.lcr_dev) && !getenv("HGE_NO_ORDER_CALL");
+                         (!b.do_fame || b.w.nrounds() == 0 || b.lcr_dev) && !hge_hooks::no_order_call();
     if (tail_ok) {
       const OrderCall oc = order_call(b, 0);
       KLAUNCH(k_order_call<16>, dim3(1), dim3(1024), 0, st, t, oc);
@@ -2424,7 +2221,7 @@ struct hge_engine {
     // memory mapped into the device: the writes cross PCIe while the later buckets
     // sort; no copy after the replay)
     int32_t* ids_dst = out_ids(b);
-    if (lazy_order && !b.order_out && !b.spl && pin_ord_dev) {
+    if (cons.lazy_order && !b.order_out && !b.spl && pin_ord_dev) {
       ids_dst = pin_ord_dev;
       b.wrote_direct = true;
     }
@@ -2464,24 +2261,24 @@ struct hge_engine {
     if (b.lcr_dev) {
       // the persisted fame and RoundEvents(LCR - 1) as below (the new LCR and its
       // call read on the device) in one launch
-      const int64_t nfrom = std::min<int64_t>(b.calls[0], n_coords);
+      const int64_t nfrom = std::min<int64_t>(b.calls[0], cons.n_coords);
       const int nb_fp = (int)div_up((int64_t)nrounds * N, 256);
-      KLAUNCH(k_fame_persist_lcre, dim3(nb_fp + std::max(1, div_up(n_coords - nfrom, 256))), dim3(256), 0, st, t,
-              (const int32_t*)c_pr, (const int32_t*)(c_pr + nrounds), (const int32_t*)(c_pr + 2 * nrounds),
-              (const int32_t*)(c_pr + 3 * nrounds), nrounds, (const int32_t*)s_clast.p, (const uint8_t*)s_dec.p,
-              nb_fp, (const int64_t*)c_nc, (const int32_t*)c_flags, lcr, (int)nfrom, (int)n_coords, lcre_out);
+      KLAUNCH(k_fame_persist_lcre, dim3(nb_fp + std::max(1, div_up(cons.n_coords - nfrom, 256))), dim3(256), 0, st, t,
+              (const int32_t*)cons.c_pr, (const int32_t*)(cons.c_pr + nrounds), (const int32_t*)(cons.c_pr + 2 * nrounds),
+              (const int32_t*)(cons.c_pr + 3 * nrounds), nrounds, (const int32_t*)s_clast.p, (const uint8_t*)s_dec.p,
+              nb_fp, (const int64_t*)cons.c_nc, (const int32_t*)cons.c_flags, cons.lcr, (int)nfrom, (int)cons.n_coords, lcre_out);
       return;
     }
     fame_persist(t, nrounds);
-    if (b.lcr_new > lcr) {
+    if (b.lcr_new > cons.lcr) {
       // RoundEvents(lcr_new - 1) at call c_set: events of that round minus the
       // ones inserted after that call
       b.lcr_up = true;
       const int r = b.lcr_new - 1;
       if (r >= 0) {
-        const int64_t nfrom = std::min<int64_t>(b.calls[b.c_set], n_coords);
-        KLAUNCH(k_lcre, dim3(std::max(1, div_up(n_coords - nfrom, 256))), dim3(256), 0, st, t,
-                (int)nfrom, (int)n_coords, r, lcre_out);
+        const int64_t nfrom = std::min<int64_t>(b.calls[b.c_set], cons.n_coords);
+        KLAUNCH(k_lcre, dim3(std::max(1, div_up(cons.n_coords - nfrom, 256))), dim3(256), 0, st, t,
+                (int)nfrom, (int)cons.n_coords, r, lcre_out);
       }
     }
   }
@@ -2490,27 +2287,27 @@ struct hge_engine {
   // delivered to the pinned order buffer), ConsensusTransactions, the undetermined count
   void commit_order(const hge_plan::Results& r, int ncalls, bool to_log, std::vector<int32_t>* order_out,
                     std::vector<int64_t>* counts_out) {
-    if (to_log) consensus.insert(consensus.end(), r.ids, r.ids + r.nrecv);
-    ctx += (int64_t)r.ntx;
+    if (to_log) cons.consensus.insert(cons.consensus.end(), r.ids, r.ids + r.nrecv);
+    cons.ctx += (int64_t)r.ntx;
     if (order_out) order_out->insert(order_out->end(), r.ids, r.ids + r.nrecv);
     if (counts_out)
       for (int c = 0; c < ncalls; c++) counts_out->push_back(r.counts[c]);
-    n_und = r.n_und;
+    cons.n_und = r.n_und;
   }
   void commit_lcr(int lcr_new, int lcr_events) {
-    lcr = lcr_new;
-    lcre = lcr_new - 1 >= 0 ? lcr_events : 0;
+    cons.lcr = lcr_new;
+    cons.lcre = lcr_new - 1 >= 0 ? lcr_events : 0;
   }
 
   // the batch's one closing round trip (read in place from the pinned arena); a
   // replay's order stays in HBM (lazy: counters, per-call counts and transaction sums only)
   void close_batch(Batch& b) {
-    const bool lazy = b.got_order && lazy_order && !b.order_out;
+    const bool lazy = b.got_order && cons.lazy_order && !b.order_out;
     const size_t off = d2h_pinned(s_out.p, 4 * (b.got_order && !lazy ? b.out.total() : b.out.header()));
     const size_t off_tx = lazy ? d2h_pinned(s_out.p + b.out.o_tx, 4 * 2 * (size_t)b.out.ntxb) : 0;
     sync();
-    const int32_t* ho = (const int32_t*)(pin.p + off);
-    const int32_t* htx = !b.got_order ? nullptr : lazy ? (const int32_t*)(pin.p + off_tx) : ho + b.out.o_tx;
+    const int32_t* ho = (const int32_t*)xfer.at(off);
+    const int32_t* htx = !b.got_order ? nullptr : lazy ? (const int32_t*)xfer.at(off_tx) : ho + b.out.o_tx;
     const hge_plan::Results r = hge_plan::parse_results(b.out, ho, htx);
     if (b.got_order) {
       if (lazy) {  // delivered into the pinned order buffer (sized at hge_replay_prepare)
@@ -2522,13 +2319,13 @@ struct hge_engine {
         }
         // the delivery's wall time after the sorts (hge_stage_times [5]; ~0 when written direct)
         stage_ms[5] = (float)((now_ns() - td) / 1e6);
-        cons_pin_n = r.nrecv;
+        cons.cons_pin_n = r.nrecv;
       }
       commit_order(r, b.ncalls, !lazy, b.order_out, b.counts_out);
     } else if (b.do_order && b.counts_out && !b.split_done) {
       for (int c = 0; c < b.ncalls; c++) b.counts_out->push_back(0);
     }
-    if (b.lcr_dev && r.lcr > lcr) {
+    if (b.lcr_dev && r.lcr > cons.lcr) {
       b.lcr_up = true;
       b.lcr_new = r.lcr;
     }
@@ -2537,7 +2334,7 @@ struct hge_engine {
 
   // split replay: the parts' fame decisions (each part's pairs [P0, P1)) all-gathered
   void split_exchange_dec(const std::vector<int32_t>& pr_round, const std::vector<int32_t>& pr_off, int npairs) {
-    const int G = sp.nparts, nr = (int)pr_round.size();
+    const int G = strm.sp.nparts, nr = (int)pr_round.size();
     std::vector<int64_t> P0(G), P1(G);
     int64_t mx = 1;
     for (int g = 0; g < G; g++) {
@@ -2549,13 +2346,13 @@ struct hge_engine {
     }
     const int64_t bytes = (mx * N + 255) / 256 * 256;
     uint8_t* buf = (uint8_t*)x_buf(bytes);
-    const int p = sp.part;
+    const int p = strm.sp.part;
     if (P1[p] > P0[p])
       HGE_HIPCHK(hipMemcpyAsync(buf + (size_t)p * bytes, s_dec.p + (size_t)P0[p] * N, (size_t)(P1[p] - P0[p]) * N,
                             hipMemcpyDeviceToDevice, st));
     x_gather(bytes, buf);
     if (emulating()) {  // the other parts' decisions of this fame iteration, from the record
-      const std::vector<uint8_t>& rd = rec_dec.at((size_t)x_iter);
+      const std::vector<uint8_t>& rd = rec_dec.at((size_t)cons.x_iter);
       for (int g = 0; g < G; g++)
         if (g != p && P1[g] > P0[g]) h2d(buf + (size_t)g * bytes, rd.data() + (size_t)P0[g] * N, (size_t)(P1[g] - P0[g]) * N);
     }
@@ -2571,18 +2368,18 @@ struct hge_engine {
   void split_commit(const int32_t* o_cnt, const int32_t* o_cc, const int32_t* o_ids, int ntxb,
                     const unsigned long long* ntx_part, std::vector<int32_t>* order_out,
                     std::vector<int64_t>* counts_out) {
-    const int G = sp.nparts, p = sp.part;
+    const int G = strm.sp.nparts, p = strm.sp.part;
     int maxcalls = 0;
     int64_t cap = 1;
     for (int g = 0; g < G; g++) {
-      maxcalls = std::max(maxcalls, sp.cb[g + 1] - sp.cb[g]);
-      cap = std::max(cap, sp.a[g + 1] - sp.clo[g]);
+      maxcalls = std::max(maxcalls, strm.sp.cb[g + 1] - strm.sp.cb[g]);
+      cap = std::max(cap, strm.sp.a[g + 1] - strm.sp.clo[g]);
     }
     const SplitSlot L = SplitSlot::make(maxcalls, cap);
     const int64_t bytes = 4 * L.words;
     int32_t* buf = (int32_t*)x_buf(bytes);
-    KLAUNCH(k_split_pack, dim3(std::min(div_up(cap, 256), 4096)), dim3(256), 0, st, o_cnt, o_cc, sp.cb[p],
-            sp.cb[p + 1] - sp.cb[p], o_ids, (const int32_t*)d_und.p, (const int32_t*)d_rr.p,
+    KLAUNCH(k_split_pack, dim3(std::min(div_up(cap, 256), 4096)), dim3(256), 0, st, o_cnt, o_cc, strm.sp.cb[p],
+            strm.sp.cb[p + 1] - strm.sp.cb[p], o_ids, (const int32_t*)d_und.p, (const int32_t*)d_rr.p,
             (const int64_t*)d_cts.p, ntx_part, ntxb, (const int32_t*)(s_small.p + 8), L,
             buf + (size_t)p * L.words);
     x_gather(bytes, buf);
@@ -2590,7 +2387,7 @@ struct hge_engine {
       int64_t off0 = 0;
       for (int g = 0; g < G; g++) {
         int64_t nord = 0;
-        for (int c = sp.cb[g]; c < sp.cb[g + 1]; c++) nord += rec_counts[c];
+        for (int c = strm.sp.cb[g]; c < strm.sp.cb[g + 1]; c++) nord += rec_counts[c];
         if (g != p) {
           const bool last = g == G - 1;
           std::vector<int32_t> sl((size_t)L.words, 0);
@@ -2600,11 +2397,11 @@ struct hge_engine {
             sl[L.ids + i] = x;
             sl[L.rr + i] = rec_rr[x];
             memcpy(&sl[L.cts + 2 * i], &rec_cts[x], 8);
-            tx += (unsigned long long)h_ntx[x];
+            tx += (unsigned long long)strm.log.h_ntx[x];
           }
           const int64_t nleft = last ? (int64_t)rec_left.size() : 0;
           for (int64_t i = 0; i < nleft; i++) sl[L.left + i] = rec_left[i];
-          for (int c = sp.cb[g]; c < sp.cb[g + 1]; c++) sl[L.counts + (c - sp.cb[g])] = (int32_t)rec_counts[c];
+          for (int c = strm.sp.cb[g]; c < strm.sp.cb[g + 1]; c++) sl[L.counts + (c - strm.sp.cb[g])] = (int32_t)rec_counts[c];
           sl[0] = (int32_t)nord;
           sl[1] = (int32_t)nleft;
           sl[4] = (int32_t)(uint32_t)tx;
@@ -2641,26 +2438,14 @@ struct hge_engine {
                             hipMemcpyDeviceToDevice, st));
     const size_t po = d2h_pinned(s_sord.p, 4 * (size_t)tot);
     sync();
-    const int32_t* ids = (const int32_t*)(pin.p + po);
-    consensus.insert(consensus.end(), ids, ids + tot);
+    const int32_t* ids = (const int32_t*)xfer.at(po);
+    cons.consensus.insert(cons.consensus.end(), ids, ids + tot);
     if (order_out) order_out->insert(order_out->end(), ids, ids + tot);
-    ctx += (int64_t)ntx;
-    n_und = nleft;
+    cons.ctx += (int64_t)ntx;
+    cons.n_und = nleft;
     if (counts_out)
       for (int g = 0; g < G; g++)
-        for (int c = sp.cb[g]; c < sp.cb[g + 1]; c++) counts_out->push_back(hd[(size_t)g * L.ids + 8 + (c - sp.cb[g])]);
-  }
-
-  void gather_rounds(const std::vector<int32_t>& ids, std::vector<int32_t>& out) {
-    // contiguous-range copy of d_round covering all ids
-    int lo = INF32, hi = -1;
-    for (int v : ids) {
-      lo = std::min(lo, v);
-      hi = std::max(hi, v);
-    }
-    std::vector<int32_t> r(hi - lo + 1);
-    readback(r.data(), d_round.p + lo, r.size());
-    for (size_t k = 0; k < ids.size(); k++) out[k] = r[ids[k] - lo];
+        for (int c = strm.sp.cb[g]; c < strm.sp.cb[g + 1]; c++) counts_out->push_back(hd[(size_t)g * L.ids + 8 + (c - strm.sp.cb[g])]);
   }
 
   void scan_large(const int32_t* in, int32_t* out, int n, int32_t* total) {
@@ -2684,36 +2469,36 @@ struct hge_engine {
   void fame_decide(const Tables& t, const hge_plan::FameWindows& w, int npairs, bool timeline = true) {
     const int nrounds = w.nrounds();
     int win_lo = 0, win_hi = nrounds;
-    if (split_on()) split_rounds_of(sp.part, w.round, win_lo, win_hi);
+    if (split_on()) split_rounds_of(strm.sp.part, w.round, win_lo, win_hi);
     const int p0 = win_lo < nrounds ? w.off[win_lo] : npairs;
     const int p1 = win_hi < nrounds ? w.off[win_hi] : npairs;
     if (p1 > p0 && N == 64 * NW) {
-      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3(p1 - p0), dim3(N), 0, st, t, c_pr + win_lo,
-                 c_pr + nrounds + win_lo, c_pr + 2 * nrounds + win_lo, win_hi - win_lo, p0, p1, c_nc, c_Rc, s_dec.p,
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide_blk, dim3(p1 - p0), dim3(N), 0, st, t, cons.c_pr + win_lo,
+                 cons.c_pr + nrounds + win_lo, cons.c_pr + 2 * nrounds + win_lo, win_hi - win_lo, p0, p1, cons.c_nc, cons.c_Rc, s_dec.p,
                  (const int32_t*)nullptr);
     } else if (p1 > p0) {
-      KLAUNCH_NW(NW, NW_PT, k_fame_decide, dim3(div_up((p1 - p0) * N, 256)), dim3(256), 0, st, t, c_pr + win_lo,
-                 c_pr + nrounds + win_lo, c_pr + 2 * nrounds + win_lo, win_hi - win_lo, p0, p1, c_nc, c_Rc, s_dec.p);
+      KLAUNCH_NW(NW, NW_PT, k_fame_decide, dim3(div_up((p1 - p0) * N, 256)), dim3(256), 0, st, t, cons.c_pr + win_lo,
+                 cons.c_pr + nrounds + win_lo, cons.c_pr + 2 * nrounds + win_lo, win_hi - win_lo, p0, p1, cons.c_nc, cons.c_Rc, s_dec.p);
     }
     if (split_on()) split_exchange_dec(w.round, w.off, npairs);
     if (!timeline) return;
     const int G = group_lanes();
     const dim3 tgrid(div_up((int64_t)nrounds * G, 256));
-    const int32_t *pr_off = c_pr + nrounds, *pr_cf = c_pr + 2 * nrounds, *pr_len = c_pr + 3 * nrounds;
+    const int32_t *pr_off = cons.c_pr + nrounds, *pr_cf = cons.c_pr + 2 * nrounds, *pr_len = cons.c_pr + 3 * nrounds;
     if (G == 16) {
-      KLAUNCH((k_fame_timeline_g<16, 1>), tgrid, dim3(256), 0, st, t, c_pr, pr_off, pr_cf, pr_len, nrounds, c_nc,
-              s_dec.p, s_decbit.p, c_Lc);
+      KLAUNCH((k_fame_timeline_g<16, 1>), tgrid, dim3(256), 0, st, t, cons.c_pr, pr_off, pr_cf, pr_len, nrounds, cons.c_nc,
+              s_dec.p, s_decbit.p, cons.c_Lc);
     } else if (G == 32) {
-      KLAUNCH((k_fame_timeline_g<32, 1>), tgrid, dim3(256), 0, st, t, c_pr, pr_off, pr_cf, pr_len, nrounds, c_nc,
-              s_dec.p, s_decbit.p, c_Lc);
+      KLAUNCH((k_fame_timeline_g<32, 1>), tgrid, dim3(256), 0, st, t, cons.c_pr, pr_off, pr_cf, pr_len, nrounds, cons.c_nc,
+              s_dec.p, s_decbit.p, cons.c_Lc);
     } else {
-      KLAUNCH_NW(NW, NW_PAT, k_fame_timeline_g, 64, tgrid, dim3(256), 0, st, t, c_pr, pr_off, pr_cf, pr_len,
-                 nrounds, c_nc, s_dec.p, s_decbit.p, c_Lc);
+      KLAUNCH_NW(NW, NW_PAT, k_fame_timeline_g, 64, tgrid, dim3(256), 0, st, t, cons.c_pr, pr_off, pr_cf, pr_len,
+                 nrounds, cons.c_nc, s_dec.p, s_decbit.p, cons.c_Lc);
     }
   }
   void fame_persist(const Tables& t, int nrounds) {
-    KLAUNCH(k_fame_persist, dim3(div_up((int64_t)nrounds * N, 256)), dim3(256), 0, st, t, c_pr, c_pr + nrounds,
-            c_pr + 2 * nrounds, c_pr + 3 * nrounds, nrounds, s_clast.p, s_dec.p);
+    KLAUNCH(k_fame_persist, dim3(div_up((int64_t)nrounds * N, 256)), dim3(256), 0, st, t, cons.c_pr, cons.c_pr + nrounds,
+            cons.c_pr + 2 * nrounds, cons.c_pr + 3 * nrounds, nrounds, s_clast.p, s_dec.p);
   }
 
   // the end of a bulk replay that took its median from the FD rows: the rows of the
@@ -2721,7 +2506,7 @@ struct hge_engine {
   // lowest such position of every chain.  The new undetermined list and its count are on
   // the device (bucket_and_sort): no round trip.
   void fdtd_tail(const Batch& b) {
-    if (!fdtd_stale) return;
+    if (!cons.fdtd_stale) return;
     if (!b.got_order || b.spl || !b.commit) {  // (no new list on the device: all of it)
       ensure_fdtd();
       return;
@@ -2731,8 +2516,8 @@ struct hge_engine {
             (const int32_t*)d_creator.p, (const int32_t*)d_index.p, (const int32_t*)d_und.p,
             (const int32_t*)out_word(hge_plan::ResultsLayout::kUndetermined), s_fdlo.p);
     // (mostly a tile or two per chain; the kernel loops where more is left)
-    fdtd_pass("fdtd_tail (k_fd_transpose_ts<uint16_t>)", std::min(div_up(std::max(fdtd_maxlen, 1), 64), 4));
-    fdtd_stale = false;
+    fdtd_pass("fdtd_tail (k_fd_transpose_ts<uint16_t>)", std::min(div_up(std::max(cons.fdtd_maxlen, 1), 64), 4));
+    cons.fdtd_stale = false;
   }
 
   // round received per candidate and its consensus timestamp.  N > 16: the median is a
@@ -2742,7 +2527,7 @@ struct hge_engine {
   // (candidate q = event q).
   void recv_dispatch(Batch& b) {
     const bool wmed = N > 16;
-    const bool ident = b.fresh_und && b.cand == d_und.p && (int64_t)b.ncand == n_events;
+    const bool ident = b.fresh_und && b.cand == d_und.p && (int64_t)b.ncand == strm.log.n_events;
     int32_t* bseg = nullptr;
     if (wmed) {
       s_bseg.need(b.ncand);
@@ -2751,14 +2536,14 @@ struct hge_engine {
     }
     const Tables t = tables();
     KLAUNCH_NW(NW, NW_T, k_round_received, dim3(div_up(b.ncand, 256)), dim3(256), 0, st, t, b.cand, b.ncand,
-               vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p, b.ncalls, 0, b.rr_lo, b.R_last,
-               segoff_p, s_segcnt.p, s_segcall.p, s_segdec.p, s_segfws.p, s_theta.p, s_recv.p, s_rr.p, s_cts.p,
+               cons.vis_all ? (const int32_t*)nullptr : (const int32_t*)s_vis.p, b.ncalls, 0, b.rr_lo, b.R_last,
+               cons.segoff_p, s_segcnt.p, s_segcall.p, s_segdec.p, s_segfws.p, s_theta.p, s_recv.p, s_rr.p, s_cts.p,
                bseg);
-    if (wmed && ident && fdtd_stale && !test_rows_fallback) {
+    if (wmed && ident && cons.fdtd_stale && !test_rows_fallback) {
       // a bulk replay whose coordinate step skipped the timestamps: the median from the FD rows
       // (16 positions x 512 threads measured fastest of seven shapes)
       constexpr int TQ = 16, NT = 512;
-      const int64_t nb = (int64_t)N * div_up(fdtd_maxlen, TQ);
+      const int64_t nb = (int64_t)N * div_up(cons.fdtd_maxlen, TQ);
       KLAUNCH_AS("k_median_rows<16, 512>", (k_median_rows<TQ, NT>), dim3((unsigned)nb), dim3(NT),
                  sizeof(int32_t) * TQ * (N + 4), st, t, (const int32_t*)(s_fdlo.p + N), (const int32_t*)s_recv.p,
                  (const int32_t*)s_rr.p, (const int32_t*)bseg, (const uint64_t*)s_segfws.p, s_cts.p);
@@ -2770,25 +2555,24 @@ struct hge_engine {
   }
 
   // DivideRounds: everything inserted becomes visible to the consensus calls
-  bool dividing = false, und_appended = false;
   void divide() {
-    dividing = true;
-    und_appended = false;
+    cons.dividing = true;
+    cons.und_appended = false;
     try {
       coords();
     } catch (...) {
-      dividing = false;
+      cons.dividing = false;
       throw;
     }
-    dividing = false;
-    if (n_divided < n_coords) {
+    cons.dividing = false;
+    if (cons.n_divided < cons.n_coords) {
       // append the newly divided events to the undetermined list (insertion order),
       // unless k_round_assign already did
-      const int64_t a = n_divided, m = n_coords - n_divided;
-      ensure_events(n_coords);
-      if (!und_appended) KLAUNCH(k_iota, dim3(div_up(m, 256)), dim3(256), 0, st, d_und.p + n_und, m, (int32_t)a);
-      n_und += m;
-      n_divided = n_coords;
+      const int64_t a = cons.n_divided, m = cons.n_coords - cons.n_divided;
+      ensure_events(cons.n_coords);
+      if (!cons.und_appended) KLAUNCH(k_iota, dim3(div_up(m, 256)), dim3(256), 0, st, d_und.p + cons.n_und, m, (int32_t)a);
+      cons.n_und += m;
+      cons.n_divided = cons.n_coords;
     }
     update_rdiv();
   }
@@ -2802,42 +2586,42 @@ struct hge_engine {
   // at most one per new event).  Returns false (nothing done) when the call does not
   // fit this path.
   bool online_fast(std::vector<int32_t>& order) {
-    const int64_t n0 = n_coords, n1 = n_events, m = n1 - n0;
-    if (N > 16 || m <= 0 || R == 0 || cstep || split_on() || rec_on || ext_on || sp_active) return false;
-    if (n_divided != n0 || !la_seq_ok(m) || n_und + m > 65536 || n_und + m > SCAN_LDS) return false;
-    if (getenv("HGE_NO_ONLINE_FAST")) return false;
-    if (*std::max_element(chain_len.begin(), chain_len.end()) + 1 >= 0xFFFF) return false;
+    const int64_t n0 = cons.n_coords, n1 = strm.log.n_events, m = n1 - n0;
+    if (N > 16 || m <= 0 || cons.R == 0 || cons.cstep || split_on() || rec_on || cons.ext_on || strm.sp_active) return false;
+    if (cons.n_divided != n0 || !la_seq_ok(m) || cons.n_und + m > 65536 || cons.n_und + m > SCAN_LDS) return false;
+    if (hge_hooks::no_online_fast()) return false;
+    if (*std::max_element(strm.log.chain_len.begin(), strm.log.chain_len.end()) + 1 >= 0xFFFF) return false;
     consensus_sync();
-    ensure_rcap((int64_t)R + m + 4);
+    ensure_rcap((int64_t)cons.R + m + 4);
     // ---- divide(): coordinates and rounds, no readback
-    dividing = true;
-    und_appended = false;
+    cons.dividing = true;
+    cons.und_appended = false;
     if (!coords_a()) {
-      dividing = false;
+      cons.dividing = false;
       throw Error(HGE_ERR_INTERNAL, "online call: no coordinates to compute");
     }
-    if (!cstep || !cstep->frontier_started)
+    if (!cons.cstep || !cons.cstep->frontier_started)
       throw Error(HGE_ERR_INTERNAL, "online call: frontier start not fused");
-    CoordStep s = *cstep;
-    cstep.reset();
+    CoordStep s = *cons.cstep;
+    cons.cstep.reset();
     // (n_divided == n0 and at most 65,536 candidates: the walk's block appends the new
     // ids, assigns their rounds and does the rounds tail)
     walk_online(s);
-    dividing = false;
-    n_coords = n1;
-    coords_len = chain_len;
-    n_und += m;
-    n_divided = n_coords;
-    und_fresh = false;
+    cons.dividing = false;
+    cons.n_coords = n1;
+    cons.coords_len = strm.log.chain_len;
+    cons.n_und += m;
+    cons.n_divided = cons.n_coords;
+    cons.und_fresh = false;
     // ---- consensus of the one call, control built on the device
-    const int Rmax = R + (int)m + 1;
-    const int nround_max = std::max(1, Rmax - 2 - lcr), nr_max = std::max(1, Rmax);
+    const int Rmax = cons.R + (int)m + 1;
+    const int nround_max = std::max(1, Rmax - 2 - cons.lcr), nr_max = std::max(1, Rmax);
     Batch b;
-    b.calls = &n_divided;
+    b.calls = &cons.n_divided;
     b.ncalls = 1;
     b.do_fame = b.do_order = b.commit = b.ord = true;
     b.cand = d_und.p;
-    b.ncand = (int)n_und;
+    b.ncand = (int)cons.n_und;
     b.out = hge_plan::results_layout(1, b.ncand);
     b.ctl = hge_plan::ctl_layout(1, nround_max, nr_max);
     s_cctl.need(b.ctl.total);
@@ -2855,19 +2639,19 @@ struct hge_engine {
     s_theta.need(nslot * N);
     s_out.need(b.out.total());
     DynCall dc{};
-    dc.lcr = lcr;
+    dc.lcr = cons.lcr;
     dc.ncand = b.ncand;
     dc.Rcap = Rcap;
-    dc.n_c = n_divided;
+    dc.n_c = cons.n_divided;
     dc.rstate = s.rstate;
     dc.minw = d_minw.p;
-    dc.c_nc = c_nc;
-    dc.c_Rc = c_Rc;
-    dc.c_Lc = c_Lc;
-    dc.c_flags = c_flags;
-    dc.c_pr = c_pr;
-    dc.c_pidx = c_pidx;
-    dc.c_sgo = c_sgo;
+    dc.c_nc = cons.c_nc;
+    dc.c_Rc = cons.c_Rc;
+    dc.c_Lc = cons.c_Lc;
+    dc.c_flags = cons.c_flags;
+    dc.c_pr = cons.c_pr;
+    dc.c_pidx = cons.c_pidx;
+    dc.c_sgo = cons.c_sgo;
     dc.dec = s_dec.p;
     dc.decbit = s_decbit.p;
     dc.LCR = s_LCR.p;
@@ -2880,1050 +2664,93 @@ struct hge_engine {
     const size_t off = d2h_pinned(s_out.p, 4 * b.out.total());
     const size_t offw = d2h_pinned(d_minw.p, 4 * ((size_t)Rcap + hge_plan::kTailPartial));
     sync();
-    const int32_t* hw = (const int32_t*)(pin.p + offw);
+    const int32_t* hw = (const int32_t*)xfer.at(offw);
     const hge_plan::RoundsTail rt = hge_plan::parse_rounds_tail(hw + Rcap, 0);
     if (rt.overflow) {  // (unreachable: ensure_rcap covers R + m + 4) the host state has moved on: refuse later calls
-      failed = "online call: rounds table overflow past its bound";
-      throw Error(HGE_ERR_INTERNAL, failed);
+      strm.failed = "online call: rounds table overflow past its bound";
+      throw Error(HGE_ERR_INTERNAL, strm.failed);
     }
-    R = rt.R;
-    h_minw.assign(hw, hw + R);
-    minw_full = false;
-    mnr_key[0] = -1;
+    cons.R = rt.R;
+    cons.h_minw.assign(hw, hw + cons.R);
+    cons.minw_full = false;
+    cons.mnr_key[0] = -1;
     update_rdiv();
-    const int32_t* ho = (const int32_t*)(pin.p + off);
+    const int32_t* ho = (const int32_t*)xfer.at(off);
     const hge_plan::Results r = hge_plan::parse_results(b.out, ho, ho + b.out.o_tx);
     commit_order(r, 1, true, &order, nullptr);
-    if (r.lcr > lcr) commit_lcr(r.lcr, r.lcr_events);
-    prof_collect();
+    if (r.lcr > cons.lcr) commit_lcr(r.lcr, r.lcr_events);
+    prof.collect();
     return true;
   }
 
   // first witness id of every round (host copy: Rounds() as seen at any event count)
   void update_rdiv() {
     // h_minw was read back together with the round count (coords)
-    h_minw.resize(R);
-    if (R == 0) {
-      R_div = 0;
+    cons.h_minw.resize(cons.R);
+    if (cons.R == 0) {
+      cons.R_div = 0;
       return;
     }
-    R_div = (int)(std::lower_bound(h_minw.begin(), h_minw.end(),
-                                   (int32_t)std::min<int64_t>(n_divided, INF32)) -
-                  h_minw.begin());
+    cons.R_div = (int)(std::lower_bound(cons.h_minw.begin(), cons.h_minw.end(),
+                                   (int32_t)std::min<int64_t>(cons.n_divided, INF32)) -
+                  cons.h_minw.begin());
   }
+
+  // A fresh replay in two halves: replay_begin (reset + coordinates) and
+  // replay_end (rounds frontier, DivideRounds/DecideFame/FindOrder at every call);
+  // the cross-GPU split runs the walkers and their join between the two.
+  void replay_begin() {
+    // fresh consensus state over the staged events (they stay resident in HBM)
+    cons = ConsensusState(N);
+    cons.w_start = std::chrono::steady_clock::now();
+    reset_rounds();
+    HGE_HIPCHK(hipEventRecord(ev[0], st));
+    coords_a();
+  }
+
+  void replay_end(int64_t* n_ordered) {
+    const int64_t keep = strm.log.n_events;
+    if (cons.cstep) coords_b();
+    HGE_HIPCHK(hipEventRecord(ev[1], st));
+    const auto w1 = std::chrono::steady_clock::now();
+    cons.n_divided = keep;
+    update_rdiv();
+    if (keep > 0) fill_iota(d_und.p, keep, 0);
+    cons.n_und = keep;
+    cons.und_fresh = keep > 0;
+    cons.replay_counts.clear();
+    // the consensus log (fresh since replay_begin) is the replay's order, delivered to the
+    // pinned order buffer in one copy (not staged through the arena into the log's vector)
+    cons.lazy_order = pin_ord.n >= (size_t)keep;
+    try {
+      consensus_batch(strm.replay_calls, true, true, true, nullptr, &cons.replay_counts);
+    } catch (...) {
+      cons.lazy_order = false;
+      throw;
+    }
+    cons.lazy_order = false;
+    HGE_HIPCHK(hipEventRecord(ev[2], st));
+    HGE_HIPCHK(hipEventSynchronize(ev[2]));
+    const auto w2 = std::chrono::steady_clock::now();
+    float a = 0, b = 0;
+    HGE_HIPCHK(hipEventElapsedTime(&a, ev[0], ev[1]));
+    HGE_HIPCHK(hipEventElapsedTime(&b, ev[1], ev[2]));
+    auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
+      return (float)std::chrono::duration<double, std::milli>(y - x).count();
+    };
+    // [0] coordinates+rounds on the GPU, [1] their wall time, [2] consensus wall time,
+    // [3] consensus on the GPU, [4] replay wall time, [5] the order's delivery to host
+    // memory (wall, inside [2]), [6] GPU total
+    stage_ms[0] = a;
+    stage_ms[1] = ms(cons.w_start, w1);
+    stage_ms[2] = ms(w1, w2);
+    stage_ms[3] = b;
+    stage_ms[4] = ms(cons.w_start, w2);
+    stage_ms[6] = a + b;
+    if (n_ordered) *n_ordered = consensus_size();
+    dbg_dump();
+  }
+
 };
 
-// ---------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------
-#define GUARD_BEGIN try {
-#define REFUSE_IF_FAILED(h) \
-  if (!(h)->failed.empty()) throw Error(HGE_ERR_INTERNAL, "engine state inconsistent since: " + (h)->failed);
-#define GUARD_END(h)                 \
-  }                                  \
-  catch (Error & e) {                \
-    (h)->err = e.msg;                \
-    return e.code;                   \
-  }                                  \
-  catch (std::exception & e) {       \
-    (h)->err = e.what();             \
-    return HGE_ERR_INTERNAL;         \
-  }
-
-extern "C" {
-
-int hge_create(int32_t n_participants, int64_t capacity_events, int32_t device, uint32_t flags,
-               hge_engine** out) {
-  (void)flags;
-  if (!out || n_participants < 1 || n_participants > 256) return HGE_ERR_ARG;
-  hge_engine* h = new hge_engine();
-  try {
-    h->init(n_participants, capacity_events, device);
-  } catch (Error& e) {
-    fprintf(stderr, "hge_create: %s\n", e.msg.c_str());
-    delete h;
-    *out = nullptr;
-    return e.code;
-  }
-  *out = h;
-  return HGE_OK;
-}
-
-void hge_destroy(hge_engine* h) {
-  delete h;
-}
-
-const char* hge_last_error(hge_engine* h) { return h ? h->err.c_str() : "null handle"; }
-
-int hge_reset(hge_engine* h) {
-  GUARD_BEGIN
-  h->reset_state();
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_insert_events(hge_engine* h, const hge_event* ev, int64_t n, int32_t* status_out,
-                      int64_t* n_accepted) {
-  GUARD_BEGIN
-  REFUSE_IF_FAILED(h)
-  const int64_t c0 = hge_engine::now_ns();
-  int64_t acc = 0;
-  int rc = HGE_OK;
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t sp = ev[i].self_parent, op = ev[i].other_parent;
-    int r = h->admit(ev[i], sp, op);
-    if (r != HGE_OK) {
-      if (status_out) status_out[i] = r;
-      rc = r;
-      break;
-    }
-    if (status_out) status_out[i] = (int32_t)h->n_events;
-    h->append(ev[i], sp, op);
-    acc++;
-  }
-  if (n_accepted) *n_accepted = acc;
-  h->hp.insert_ns += hge_engine::now_ns() - c0;
-  return rc;
-  GUARD_END(h)
-}
-
-int hge_divide_rounds(hge_engine* h) {
-  GUARD_BEGIN
-  REFUSE_IF_FAILED(h)
-  h->divide();
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_decide_fame(hge_engine* h) {
-  GUARD_BEGIN
-  REFUSE_IF_FAILED(h)
-    h->consensus_batch({h->n_divided}, true, false, false, nullptr, nullptr);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_decide_round_received(hge_engine* h) {
-  GUARD_BEGIN
-  REFUSE_IF_FAILED(h)
-    h->consensus_batch({h->n_divided}, false, true, false, nullptr, nullptr);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_find_order(hge_engine* h, int32_t* ids_out, int64_t cap, int64_t* n_out) {
-  GUARD_BEGIN
-  REFUSE_IF_FAILED(h)
-    std::vector<int32_t> order;
-  h->consensus_batch({h->n_divided}, false, true, true, &order, nullptr);
-  for (int64_t i = 0; i < (int64_t)order.size() && i < cap && ids_out; i++) ids_out[i] = order[i];
-  if (n_out) *n_out = (int64_t)order.size();
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_run_consensus(hge_engine* h, int32_t* ids_out, int64_t cap, int64_t* n_out) {
-  GUARD_BEGIN
-  REFUSE_IF_FAILED(h)
-  const int64_t c0 = hge_engine::now_ns();
-  std::vector<int32_t> order;
-  if (!h->online_fast(order)) {
-    h->divide();
-    h->consensus_batch({h->n_divided}, true, true, true, &order, nullptr);
-  }
-  for (int64_t i = 0; i < (int64_t)order.size() && i < cap && ids_out; i++) ids_out[i] = order[i];
-  if (n_out) *n_out = (int64_t)order.size();
-  h->hp.calls++;
-  h->hp.call_ns += hge_engine::now_ns() - c0;
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_replay_prepare(hge_engine* h, const hge_event* ev, int64_t n_sub,
-                       const int64_t* call_points, int64_t n_calls, int32_t* status_out) {
-  GUARD_BEGIN
-  if (n_sub < 0 || (n_sub > 0 && !ev) || n_calls < 0 || (n_calls > 0 && !call_points)) {
-    h->err = "hge_replay_prepare: bad argument";
-    return HGE_ERR_ARG;
-  }
-  // call points: strictly ascending submission counts in [1, n_sub]
-  for (int64_t c = 0; c < n_calls; c++) {
-    if (call_points[c] < 1 || call_points[c] > n_sub || (c > 0 && call_points[c] <= call_points[c - 1])) {
-      h->err = "hge_replay_prepare: call points must be strictly ascending within [1, n_sub]";
-      return HGE_ERR_ARG;
-    }
-  }
-  h->reset_state();
-  h->sp = hge_engine::SplitPlan();  // a plan belongs to the stream it was made for
-  h->sp_active = false;
-  std::vector<int32_t> idmap(n_sub, -1);
-  h->replay_calls.clear();
-  int64_t nc = 0;
-  for (int64_t i = 0; i < n_sub; i++) {
-    const int32_t s = ev[i].self_parent, o = ev[i].other_parent;
-    int32_t sp = s < 0 ? HGE_NONE : (s < i && idmap[s] >= 0 ? idmap[s] : HGE_UNKNOWN);
-    int32_t op = o < 0 ? HGE_NONE : (o < i && idmap[o] >= 0 ? idmap[o] : HGE_UNKNOWN);
-    int r = h->admit(ev[i], sp, op);
-    if (r == HGE_OK) {
-      idmap[i] = (int32_t)h->n_events;
-      h->append(ev[i], sp, op);
-    }
-    if (status_out) status_out[i] = r == HGE_OK ? idmap[i] : r;
-    while (nc < n_calls && call_points[nc] == i + 1) {
-      h->replay_calls.push_back(h->n_events);
-      nc++;
-    }
-  }
-  h->upload();
-  h->cons_pin_n = 0;
-  h->ensure_pin_ord((size_t)h->n_events);  // the replay's order is delivered here
-  HGE_HIPCHK(hipStreamSynchronize(h->st));
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-// A fresh replay in two halves: replay_begin (reset + coordinates) and
-// replay_end (rounds frontier, DivideRounds/DecideFame/FindOrder at every call);
-// the cross-GPU split runs the walkers and their join between the two.
-static void replay_begin(hge_engine* h) {
-  // fresh consensus state over the staged events (they stay resident in HBM)
-  h->n_coords = h->n_divided = 0;
-  h->coords_len.assign(h->N, 0);
-  h->R = 0;
-  h->h_minw.clear();
-  h->lcr = -1;
-  h->lcre = 0;
-  h->ctx = 0;
-  h->consensus.clear();
-  h->cons_pin_n = 0;
-  h->n_und = 0;
-  h->ext_on = false;
-  h->w_start = std::chrono::steady_clock::now();
-  h->reset_rounds();
-  HGE_HIPCHK(hipEventRecord(h->ev[0], h->st));
-  h->coords_a();
-}
-
-static void replay_end(hge_engine* h, int64_t* n_ordered) {
-  const int64_t keep = h->n_events;
-  if (h->cstep) h->coords_b();
-  HGE_HIPCHK(hipEventRecord(h->ev[1], h->st));
-  const auto w1 = std::chrono::steady_clock::now();
-  h->n_divided = keep;
-  h->update_rdiv();
-  if (keep > 0) h->fill_iota(h->d_und.p, keep, 0);
-  h->n_und = keep;
-  h->und_fresh = keep > 0;
-  h->replay_counts.clear();
-  // the consensus log (cleared above) is the replay's order, delivered to the pinned
-  // order buffer in one copy (not staged through the arena into the log's vector)
-  h->lazy_order = h->pin_ord.n >= (size_t)keep;
-  try {
-    h->consensus_batch(h->replay_calls, true, true, true, nullptr, &h->replay_counts);
-  } catch (...) {
-    h->lazy_order = false;
-    throw;
-  }
-  h->lazy_order = false;
-  HGE_HIPCHK(hipEventRecord(h->ev[2], h->st));
-  HGE_HIPCHK(hipEventSynchronize(h->ev[2]));
-  const auto w2 = std::chrono::steady_clock::now();
-  float a = 0, b = 0;
-  HGE_HIPCHK(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-  HGE_HIPCHK(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
-  auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
-    return (float)std::chrono::duration<double, std::milli>(y - x).count();
-  };
-  // [0] coordinates+rounds on the GPU, [1] their wall time, [2] consensus wall time,
-  // [3] consensus on the GPU, [4] replay wall time, [5] the order's delivery to host
-  // memory (wall, inside [2]), [6] GPU total
-  h->stage_ms[0] = a;
-  h->stage_ms[1] = ms(h->w_start, w1);
-  h->stage_ms[2] = ms(w1, w2);
-  h->stage_ms[3] = b;
-  h->stage_ms[4] = ms(h->w_start, w2);
-  h->stage_ms[6] = a + b;
-  if (n_ordered) *n_ordered = h->consensus_size();
-  h->dbg_dump();
-}
-
-int hge_replay_run(hge_engine* h, int64_t* n_ordered) {
-  GUARD_BEGIN
-  REFUSE_IF_FAILED(h)
-  h->sp_active = false;
-  if (h->rec_on) h->rec_dec.clear();
-  struct Bulk {  // the coordinate step of this replay alone
-    hge_engine* h;
-    ~Bulk() { h->rows_bulk = false; }
-  } bulk{h};
-  h->rows_bulk = true;
-  replay_begin(h);
-  h->rows_bulk = false;
-  replay_end(h, n_ordered);
-  if (h->rec_on) {  // hge_split_emulate: the rest of the record
-    const int64_t E = h->n_events;
-    h->consensus_sync();
-    h->rec_order = h->consensus;
-    h->rec_counts = h->replay_counts;
-    h->rec_rr.resize(E);
-    h->rec_cts.resize(E);
-    h->readback(h->rec_rr.data(), h->d_rr.p, (size_t)E);
-    h->readback(h->rec_cts.data(), h->d_cts.p, (size_t)E);
-    h->rec_left.resize(h->n_und);
-    if (h->n_und) h->readback(h->rec_left.data(), h->d_und.p, (size_t)h->n_und);
-    h->rec_on = false;
-    h->rec_have = true;
-  }
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-// ---- cross-GPU split of one hashgraph's rounds walk (babble_amd/dist.py) ----
-int hge_split_plan(hge_engine* h, int32_t part, int32_t nparts, const int64_t* ev_bounds,
-                   const int32_t* call_bounds, const int64_t* cand_lo) {
-  if (!h) return HGE_ERR_ARG;
-  GUARD_BEGIN
-  if (nparts <= 1) {
-    h->sp = hge_engine::SplitPlan();
-    return HGE_OK;
-  }
-  auto bad = [&](const char* why) {
-    h->err = std::string("hge_split_plan: ") + why;
-    return HGE_ERR_ARG;
-  };
-  if (h->N <= 32 || !h->direct_rounds() || h->wide32 || h->wide32_pending)
-    return bad("needs the wide direct rounds path (N > 32, N % 4 == 0, chains below 65,535 events)");
-  if (part < 0 || part >= nparts || !ev_bounds || !call_bounds || !cand_lo) return bad("bad argument");
-  const int64_t E = h->n_events;
-  const int ncalls = (int)h->replay_calls.size();
-  if (ev_bounds[0] != 0 || ev_bounds[nparts] != E || call_bounds[0] != 0 || call_bounds[nparts] != ncalls)
-    return bad("the bounds must cover the staged stream and its calls");
-  for (int g = 0; g < nparts; g++) {
-    if (ev_bounds[g + 1] < ev_bounds[g] || call_bounds[g + 1] <= call_bounds[g])
-      return bad("bounds must ascend and every part needs a call");
-    if (cand_lo[g] < 0 || cand_lo[g] > ev_bounds[g] || cand_lo[g] >= ev_bounds[g + 1])
-      return bad("cand_lo[p] must lie in [0, ev_bounds[p]] below ev_bounds[p + 1]");
-  }
-  if (E > INT32_MAX) return bad("stream too long");
-  h->sp.part = part;
-  h->sp.nparts = nparts;
-  h->sp.a.assign(ev_bounds, ev_bounds + nparts + 1);
-  h->sp.cb.assign(call_bounds, call_bounds + nparts + 1);
-  h->sp.clo.assign(cand_lo, cand_lo + nparts);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_split_exchange(hge_engine* h, hge_exchange_fn fn, void* ctx) {
-  if (!h) return HGE_ERR_ARG;
-  h->x_fn = fn;
-  h->x_ctx = ctx;
-  return HGE_OK;
-}
-
-int hge_split_emulate(hge_engine* h, int32_t on) {
-  if (!h) return HGE_ERR_ARG;
-  h->rec_on = on != 0;
-  h->rec_have = false;
-  h->rec_dec.clear();
-  return HGE_OK;
-}
-
-int hge_split_run(hge_engine* h, int64_t* n_ordered) {
-  if (!h) return HGE_ERR_ARG;
-  GUARD_BEGIN
-  if (h->sp.nparts <= 1) {
-    h->err = "hge_split_run: no split plan (hge_split_plan)";
-    return HGE_ERR_ARG;
-  }
-  if (!h->x_fn && !h->rec_have) {
-    h->err = "hge_split_run: no exchange (hge_split_exchange) and no record (hge_split_emulate)";
-    return HGE_ERR_ARG;
-  }
-  struct Off {  // the plan applies to this replay only
-    hge_engine* h;
-    ~Off() { h->sp_active = false; }
-  } off{h};
-  h->sp_active = true;
-  replay_begin(h);
-  replay_end(h, n_ordered);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_split_begin(hge_engine* h) {
-  GUARD_BEGIN
-  if (h->N <= 32 || !h->direct_rounds() || h->wide32 || h->wide32_pending) {
-    h->err = "the split walk needs the wide direct rounds path (N > 32, N % 4 == 0)";
-    return HGE_ERR_ARG;
-  }
-  h->sp_active = false;  // the walk-only split: every part computes everything else
-  replay_begin(h);
-  if (!h->cstep) {
-    h->err = "nothing staged (hge_replay_prepare first)";
-    return HGE_ERR_ARG;
-  }
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_frontier_guess(hge_engine* h, int32_t part, int32_t nparts, int32_t* start_out) {
-  if (!h) return HGE_ERR_ARG;
-  GUARD_BEGIN
-  if (!start_out || nparts < 1 || part < 0 || part >= nparts) {
-    h->err = "hge_frontier_guess: bad argument";
-    return HGE_ERR_ARG;
-  }
-  // part 0: the true first frontier (every chain's first event); part p: the time
-  // cut at event p * E / nparts (the first event of each chain inserted at or after it)
-  // with a split plan of nparts parts: its event bound of the part
-  const int64_t T = h->sp.nparts == nparts ? h->sp.a[part] : h->n_events * (int64_t)part / nparts;
-  for (int c = 0; c < h->N; c++) {
-    const std::vector<int32_t>& ch = h->h_chain[c];
-    const size_t k = std::lower_bound(ch.begin(), ch.end(), (int32_t)T) - ch.begin();
-    start_out[c] = k < ch.size() ? (int32_t)k : INF32;
-  }
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_frontier_walk(hge_engine* h, const int32_t* start, const int32_t* stopcut, int32_t extra,
-                      int32_t hmax, int32_t* rows_out, uint64_t* ssc_out, int32_t* nrows,
-                      int32_t* natural) {
-  GUARD_BEGIN
-  if (!h->cstep || !start || hmax < 2) return HGE_ERR_ARG;
-  const int N = h->N, NW = h->NW;
-  h->s_hist.need((size_t)hmax * N + N);
-  h->s_hssc.need((size_t)hmax * N * NW);
-  h->s_hstate.need(N + 4);
-  h->h2d(h->s_hstate.p, start, 4 * (size_t)N);
-  int32_t* cut = nullptr;
-  if (stopcut) {
-    h->s_hist.need((size_t)hmax * N + 2 * N);
-    cut = h->s_hist.p + (size_t)hmax * N + N;
-    h->h2d(cut, stopcut, 4 * (size_t)N);
-  }
-  int32_t* rstate = h->s_hstate.p + N;
-  HGE_HIPCHK(hipMemsetAsync(rstate, 0, 16, h->st));
-  h->s_bar.need(2);
-  h->s_gran.need(2 * (size_t)N);
-  HGE_HIPCHK(hipMemsetAsync(h->s_bar.p, 0, 8, h->st));
-  HGE_HIPCHK(hipMemsetAsync(h->s_gran.p, 0, 16 * (size_t)N, h->st));
-  auto lk = h->frontier_lock();  // until the walk has drained (the sync below)
-  Tables t = h->tables();
-  const int32_t* olen = h->cstep->olen;
-  const int32_t* len = h->cstep->len;
-  int rlo = 0, Rprev = 0;
-  const int32_t* rlo_dev = nullptr;
-  uint64_t* gran = h->s_gran.p;
-  int32_t* err = h->s_bar.p + 1;
-  uint64_t* ssc = h->s_hssc.p;
-  uint32_t* mb = h->walk_mb();
-  unsigned long long* paths = h->walk_paths();
-  unsigned long long* paths_next = h->s_wpaths.p + 2 * ((h->walk_seq + 1) & 1);
-  uint64_t* dbg = nullptr;
-  const int32_t* st0 = h->s_hstate.p;
-  int32_t* hist = h->s_hist.p;
-  int hm = hmax, ex = std::max(0, (int)extra), nostall = 0, force_exact = hge_engine::walk_force_exact();
-  int nomflag = 0;
-  void* args[] = {&t, &olen, &len, &rstate, &rlo, &rlo_dev, &Rprev, &gran, &err, &ssc, &mb, &dbg,
-                  &st0, &hist, &hm, &cut, &ex, &nostall, &force_exact, &nomflag, &paths, &paths_next};
-  h->prof_begin("k_rounds_direct_walk");
-  HGE_HIPCHK(h->launch_resident(h->direct_fn(), dim3(N), dim3(1024), args));
-  h->prof_end();
-  int32_t rs[2] = {0, 0}, e = 0;
-  h->d2h(rs, rstate, 8);
-  h->d2h(&e, err, 4);
-  h->sync();
-  if (e) throw Error(HGE_ERR_DEVICE, "rounds frontier hand-off timed out");
-  const int n = std::max(1, std::min(rs[0], hmax));
-  if (rows_out) h->readback(rows_out, h->s_hist.p, (size_t)n * N);
-  if (ssc_out) h->readback(ssc_out, h->s_hssc.p, (size_t)n * N * NW);
-  if (nrows) *nrows = n;
-  if (natural) *natural = rs[1] == 0 ? 1 : 0;
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_frontier_rows(hge_engine* h, int32_t from, int32_t n, int32_t* rows_out, uint64_t* ssc_out) {
-  GUARD_BEGIN
-  const int N = h->N, NW = h->NW;
-  if (from < 0 || n < 0 || (size_t)(from + n) * N > h->s_hist.n) return HGE_ERR_ARG;
-  if (rows_out && n) h->d2h(rows_out, h->s_hist.p + (size_t)from * N, 4 * (size_t)n * N);
-  if (ssc_out && n) h->d2h(ssc_out, h->s_hssc.p + (size_t)from * N * NW, 8 * (size_t)n * N * NW);
-  h->sync();
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_split_finish(hge_engine* h, const int32_t* rows, const uint64_t* ssc, int32_t nrows,
-                     int32_t natural, int64_t* n_ordered) {
-  GUARD_BEGIN
-  if (!h->cstep || !rows || nrows < 1 || (nrows > 1 && !ssc)) return HGE_ERR_ARG;
-  const int N = h->N, NW = h->NW;
-  h->ext_on = true;
-  h->ext_natural = natural != 0;
-  h->ext_rows = nrows;
-  h->ext_C.assign(rows, rows + (size_t)nrows * N);
-  h->ext_ssc.assign((size_t)nrows * N * NW, 0);
-  if (nrows > 1) std::copy(ssc + (size_t)N * NW, ssc + (size_t)nrows * N * NW, h->ext_ssc.begin() + (size_t)N * NW);
-  replay_end(h, n_ordered);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_replay_fetch(hge_engine* h, int32_t* order_out, int64_t cap, int64_t* call_counts_out) {
-  GUARD_BEGIN
-  if (order_out) {
-    // the log's vector, then the delivered tail in the pinned buffer: one copy each
-    const int64_t a = std::min<int64_t>((int64_t)h->consensus.size(), std::max<int64_t>(cap, 0));
-    if (a > 0) memcpy(order_out, h->consensus.data(), 4 * (size_t)a);
-    const int64_t b = std::min<int64_t>(h->cons_pin_n, std::max<int64_t>(cap - a, 0));
-    // (one copy thread moves ~12 GB/s: a 40 MB order takes 8 in parallel)
-    const int nt = b >= (1 << 20) ? 8 : 1;
-    std::vector<std::thread> th;
-    for (int k = 1; k < nt; k++)
-      th.emplace_back([=] {
-        const int64_t lo = b * k / nt, hi = b * (k + 1) / nt;
-        memcpy(order_out + a + lo, h->pin_ord.p + lo, 4 * (size_t)(hi - lo));
-      });
-    if (b > 0) memcpy(order_out + a, h->pin_ord.p, 4 * (size_t)(b / nt));
-    for (auto& x : th) x.join();
-  }
-  if (call_counts_out)
-    for (size_t c = 0; c < h->replay_counts.size(); c++) call_counts_out[c] = h->replay_counts[c];
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_replay_order(hge_engine* h, const int32_t** ids, int64_t* n) {
-  if (!h || !ids || !n) return HGE_ERR_ARG;
-  GUARD_BEGIN
-  if (!h->consensus.empty() || !h->cons_pin_n) h->consensus_sync();  // the whole log in one place
-  if (h->cons_pin_n) {
-    *ids = h->pin_ord.p;
-    *n = h->cons_pin_n;
-  } else {
-    *ids = h->consensus.data();
-    *n = (int64_t)h->consensus.size();
-  }
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_replay(hge_engine* h, const hge_event* ev, int64_t n_sub, const int64_t* call_points,
-               int64_t n_calls, int32_t* status_out, int32_t* order_out, int64_t cap,
-               int64_t* n_ordered, int64_t* call_counts_out) {
-  int rc = hge_replay_prepare(h, ev, n_sub, call_points, n_calls, status_out);
-  if (rc) return rc;
-  rc = hge_replay_run(h, n_ordered);
-  if (rc) return rc;
-  return hge_replay_fetch(h, order_out, cap, call_counts_out);
-}
-
-int64_t hge_event_count(hge_engine* h) { return h->n_events; }
-int32_t hge_participants(hge_engine* h) { return h->N; }
-int32_t hge_device(hge_engine* h) { return h->device; }
-int32_t hge_rounds(hge_engine* h) { return std::max(h->R_div, h->R_set); }
-int32_t hge_last_consensus_round(hge_engine* h) { return h->lcr; }
-int32_t hge_last_committed_round_events(hge_engine* h) { return h->lcre; }
-int64_t hge_consensus_transactions(hge_engine* h) { return h->ctx; }
-int64_t hge_consensus_count(hge_engine* h) { return h->consensus_size(); }
-// RollingList window (common/rolling_list.go:55-67): Add rolls the list back to
-// its last `size` items once it holds 2*size, so after `tot` adds it holds
-static int64_t window_len(int64_t tot, int64_t size) {
-  if (size <= 0 || tot <= 2 * size) return tot;
-  return size + (tot - 2 * size - 1) % size + 1;
-}
-int64_t hge_consensus_events(hge_engine* h, int32_t* ids_out, int64_t cap) {
-  try {
-    h->consensus_sync();
-  } catch (const Error& e) {
-    h->err = e.msg;
-    return -1;
-  }
-  const int64_t tot = (int64_t)h->consensus.size(), w = window_len(tot, h->cache_size);
-  for (int64_t i = 0; i < w && i < cap && ids_out; i++) ids_out[i] = h->consensus[tot - w + i];
-  return w;
-}
-int64_t hge_consensus_log(hge_engine* h, int64_t from, int32_t* ids_out, int64_t cap) {
-  try {
-    h->consensus_sync();
-  } catch (const Error& e) {
-    h->err = e.msg;
-    return -1;
-  }
-  const int64_t tot = (int64_t)h->consensus.size();
-  if (from < 0) from = 0;
-  for (int64_t i = from; i < tot && i - from < cap && ids_out; i++) ids_out[i - from] = h->consensus[i];
-  return std::max<int64_t>(0, tot - from);
-}
-int64_t hge_undetermined(hge_engine* h, int32_t* ids_out, int64_t cap) {
-  try {
-    if (ids_out && h->n_und > 0) {
-      int64_t m = std::min<int64_t>(cap, h->n_und);
-      h->readback(ids_out, h->d_und.p, m);
-    }
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-  return h->n_und;
-}
-int hge_known(hge_engine* h, int32_t* counts_out) {
-  for (int c = 0; c < h->N; c++) counts_out[c] = h->chain_len[c];
-  return HGE_OK;
-}
-
-static int32_t read1(hge_engine* h, const int32_t* p) {
-  int32_t v = -1;
-  h->readback(&v, p, 1);
-  return v;
-}
-
-int32_t hge_round_of(hge_engine* h, int32_t id) {
-  try {
-    if (id < 0 || id >= h->n_events) return -1;
-    h->coords();
-    return read1(h, h->d_round.p + id);
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-}
-int32_t hge_is_witness(hge_engine* h, int32_t id) {
-  try {
-    if (id < 0 || id >= h->n_events) return 0;
-    h->coords();
-    uint8_t v = 0;
-    h->readback(&v, h->d_wit.p + id, 1);
-    return v;
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-}
-int32_t hge_round_witness(hge_engine* h, int32_t round, int32_t creator) {
-  try {
-    if (round < 0 || round >= h->R || creator < 0 || creator >= h->N) return -1;
-    int32_t w = read1(h, h->d_W.p + (size_t)round * h->N + creator);
-    if (w >= h->n_divided) return -1;
-    return w;
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-}
-int32_t hge_fame(hge_engine* h, int32_t round, int32_t creator) {
-  try {
-    if (hge_round_witness(h, round, creator) < 0) return -1;
-    uint8_t v = 0;
-    h->readback(&v, h->d_fame.p + (size_t)round * h->N + creator, 1);
-    return v;
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-}
-int32_t hge_round_events(hge_engine* h, int32_t round) {
-  try {
-    if (round < 0 || round >= h->R) return 0;
-    return read1(h, h->d_rcnt.p + round);
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-}
-// Store.GetRound's events (RoundInfo.Events, roundInfo.go:24-60): every event of
-// round r in insertion order with its witness flag (the first event of round r is
-// its first witness: ids below h_minw[r] are not scanned)
-int hge_round_event_ids(hge_engine* h, int32_t round, int32_t* ids_out, uint8_t* witness_out, int64_t cap,
-                        int64_t* n_out) {
-  if (!h || !n_out) return HGE_ERR_ARG;
-  GUARD_BEGIN
-  *n_out = 0;
-  h->coords();
-  if (round < 0 || round >= h->R || h->n_coords == 0) return HGE_OK;
-  const int64_t lo = round < (int)h->h_minw.size() ? std::max<int64_t>(0, h->h_minw[round]) : 0;
-  const int64_t n = h->n_coords - lo;
-  if (n <= 0) return HGE_OK;
-  std::vector<int32_t> rd((size_t)n);
-  std::vector<uint8_t> wd((size_t)n);
-  h->d2h(rd.data(), h->d_round.p + lo, 4 * (size_t)n);
-  h->d2h(wd.data(), h->d_wit.p + lo, (size_t)n);
-  h->sync();
-  int64_t k = 0;
-  for (int64_t i = 0; i < n; i++) {
-    if (rd[(size_t)i] != round) continue;
-    if (k < cap) {
-      if (ids_out) ids_out[k] = (int32_t)(lo + i);
-      if (witness_out) witness_out[k] = wd[(size_t)i];
-    }
-    k++;
-  }
-  *n_out = k;
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int32_t hge_round_received(hge_engine* h, int32_t id) {
-  try {
-    if (id < 0 || id >= h->n_events) return -1;
-    return read1(h, h->d_rr.p + id);
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-}
-int64_t hge_consensus_timestamp(hge_engine* h, int32_t id) {
-  try {
-    if (id < 0 || id >= h->n_events) return 0;
-    int64_t v = 0;
-    h->readback(&v, h->d_cts.p + id, 1);
-    return v;
-  } catch (Error& e) {
-    h->err = e.msg;
-    return e.code;
-  }
-}
-
-int hge_coordinates(hge_engine* h, int32_t id, int32_t* la_out, int32_t* fd_out) {
-  GUARD_BEGIN
-  if (id < 0 || id >= h->n_events) return HGE_ERR_ARG;
-  h->coords();
-  const size_t off = ((size_t)h->h_creator[id] * h->ccap + h->h_index[id]) * h->N;
-  if (la_out) {
-    if (h->sweep16()) {  // N > 32: unpack the LA16 row (LA + 1 as uint16 pairs)
-      const size_t w = (size_t)(h->N + 1) / 2;
-      std::vector<uint32_t> row(w);
-      h->readback(row.data(), h->d_LA16.p + ((size_t)h->h_creator[id] * h->ccap + h->h_index[id]) * w, w);
-      for (int c = 0; c < h->N; c++) la_out[c] = (int32_t)((row[c >> 1] >> ((c & 1) * 16)) & 0xFFFFu) - 1;
-    } else {
-      h->readback(la_out, h->d_LA.p + off, h->N);
-    }
-  }
-  if (fd_out && h->fdt16()) {  // packed rows: FD + 1, 0xFFFF = none
-    std::vector<uint16_t> row(h->N);
-    h->readback(row.data(), (const uint16_t*)h->d_FD.p + off, h->N);
-    for (int c = 0; c < h->N; c++) fd_out[c] = row[c] == 0xFFFFu ? INF32 : (int32_t)row[c] - 1;
-    return HGE_OK;
-  }
-  if (fd_out) h->readback(fd_out, h->d_FD.p + off, h->N);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-// predicates on the materialised coordinates (hashgraph.go:83-208)
-int32_t hge_ancestor(hge_engine* h, int32_t x, int32_t y) {
-  if (x < 0 || x >= h->n_events || y < 0 || y >= h->n_events) return 0;
-  if (x == y) return 1;
-  std::vector<int32_t> la(h->N);
-  if (hge_coordinates(h, x, la.data(), nullptr)) return 0;
-  return la[h->h_creator[y]] >= h->h_index[y] ? 1 : 0;
-}
-int32_t hge_self_ancestor(hge_engine* h, int32_t x, int32_t y) {
-  if (x < 0 || x >= h->n_events || y < 0 || y >= h->n_events) return 0;
-  if (x == y) return 1;
-  return (h->h_creator[x] == h->h_creator[y] && h->h_index[x] >= h->h_index[y]) ? 1 : 0;
-}
-int32_t hge_see(hge_engine* h, int32_t x, int32_t y) { return hge_ancestor(h, x, y); }
-int32_t hge_strongly_see(hge_engine* h, int32_t x, int32_t y) {
-  if (x < 0 || x >= h->n_events || y < 0 || y >= h->n_events) return 0;
-  std::vector<int32_t> la(h->N), fd(h->N);
-  if (hge_coordinates(h, x, la.data(), nullptr)) return 0;
-  if (hge_coordinates(h, y, nullptr, fd.data())) return 0;
-  int c = 0;
-  for (int i = 0; i < h->N; i++) c += la[i] >= fd[i];
-  return c >= h->SM ? 1 : 0;
-}
-int32_t hge_oldest_self_ancestor_to_see(hge_engine* h, int32_t x, int32_t y) {
-  if (x < 0 || x >= h->n_events || y < 0 || y >= h->n_events) return -1;
-  std::vector<int32_t> fd(h->N);
-  if (hge_coordinates(h, y, nullptr, fd.data())) return -1;
-  const int cx = h->h_creator[x];
-  const int32_t a = fd[cx];
-  if (a <= h->h_index[x]) {
-    try {
-      return read1(h, h->d_chain.p + (size_t)cx * h->ccap + a);
-    } catch (Error& e) {
-      h->err = e.msg;
-      return -1;
-    }
-  }
-  return -1;
-}
-
-// ---- Store semantics and sync-path reads ----------------------------------
-int hge_set_cache_size(hge_engine* h, int64_t size) {
-  if (!h || size < 0) return HGE_ERR_ARG;
-  h->cache_size = size;
-  return HGE_OK;
-}
-int64_t hge_cache_size(hge_engine* h) { return h->cache_size; }
-
-int hge_participant_events(hge_engine* h, int32_t creator, int64_t skip, int32_t* ids_out,
-                           int64_t cap, int64_t* n_out) {
-  if (n_out) *n_out = 0;
-  if (creator < 0 || creator >= h->N) {
-    h->err = "not found";
-    return HGE_ERR_NOT_FOUND;
-  }
-  const std::vector<int32_t>& ch = h->h_chain[creator];
-  const int64_t tot = (int64_t)ch.size();
-  if (skip >= tot) return HGE_OK;
-  const int64_t oldest = tot - window_len(tot, h->cache_size);
-  if (skip < oldest) {
-    h->err = "too late";
-    return HGE_ERR_TOO_LATE;
-  }
-  if (skip < 0) skip = 0;
-  for (int64_t k = skip; k < tot && k - skip < cap && ids_out; k++) ids_out[k - skip] = ch[k];
-  if (n_out) *n_out = tot - skip;
-  return HGE_OK;
-}
-
-int32_t hge_participant_event(hge_engine* h, int32_t creator, int64_t index) {
-  if (!h || creator < 0 || creator >= h->N) return HGE_ERR_NOT_FOUND;
-  const std::vector<int32_t>& ch = h->h_chain[creator];
-  const int64_t tot = (int64_t)ch.size();
-  // RollingList.GetItem (common/rolling_list.go:42-53): index < oldestCached (>= 0),
-  // a negative index included, is ErrTooLate
-  if (index < 0 || index < tot - window_len(tot, h->cache_size)) return HGE_ERR_TOO_LATE;
-  if (index >= tot) return HGE_ERR_NOT_FOUND;
-  return ch[index];
-}
-
-int32_t hge_last_from(hge_engine* h, int32_t creator) {
-  if (creator < 0 || creator >= h->N) return HGE_ERR_NOT_FOUND;
-  return h->chain_last[creator];
-}
-
-int hge_diff(hge_engine* h, const int32_t* known, int32_t* ids_out, int64_t cap, int64_t* n_out) {
-  if (n_out) *n_out = 0;
-  if (!known) return HGE_ERR_ARG;
-  std::vector<int32_t> ids;
-  for (int c = 0; c < h->N; c++) {
-    const std::vector<int32_t>& ch = h->h_chain[c];
-    const int64_t tot = (int64_t)ch.size(), skip = known[c];
-    if (skip >= tot) continue;
-    if (skip < tot - window_len(tot, h->cache_size)) {
-      h->err = "too late";
-      return HGE_ERR_TOO_LATE;
-    }
-    for (int64_t k = std::max<int64_t>(skip, 0); k < tot; k++) ids.push_back(ch[k]);
-  }
-  std::sort(ids.begin(), ids.end());  // ByTopologicalOrder: ids are insertion order
-  for (int64_t i = 0; i < (int64_t)ids.size() && i < cap && ids_out; i++) ids_out[i] = ids[i];
-  if (n_out) *n_out = (int64_t)ids.size();
-  return HGE_OK;
-}
-
-int hge_wire_info(hge_engine* h, int32_t id, int32_t* out) {
-  if (id < 0 || id >= h->n_events || !out) return HGE_ERR_ARG;
-  const int32_t sp = h->h_sp[id], op = h->h_op[id];
-  out[0] = sp >= 0 ? h->h_index[sp] : -1;
-  out[1] = op >= 0 ? h->h_creator[op] : -1;
-  out[2] = op >= 0 ? h->h_index[op] : -1;
-  out[3] = h->h_creator[id];
-  return HGE_OK;
-}
-
-int hge_read_wire_parents(hge_engine* h, int32_t creator_id, int32_t self_parent_index,
-                          int32_t other_parent_creator_id, int32_t other_parent_index,
-                          int32_t* sp_out, int32_t* op_out) {
-  if (creator_id < 0 || creator_id >= h->N) return HGE_ERR_NOT_FOUND;
-  int32_t sp = HGE_NONE, op = HGE_NONE;
-  if (self_parent_index >= 0) {
-    sp = hge_participant_event(h, creator_id, self_parent_index);
-    if (sp < 0) return sp;
-  }
-  if (other_parent_index >= 0) {
-    op = hge_participant_event(h, other_parent_creator_id, other_parent_index);
-    if (op < 0) return op;
-  }
-  if (sp_out) *sp_out = sp;
-  if (op_out) *op_out = op;
-  return HGE_OK;
-}
-
-// ---- bulk state reads ------------------------------------------------------
-int hge_event_rounds(hge_engine* h, int32_t* round_out, uint8_t* witness_out, int64_t cap) {
-  GUARD_BEGIN
-  h->coords();
-  const int64_t m = std::min<int64_t>(cap, h->n_events);
-  if (m > 0 && round_out) h->d2h(round_out, h->d_round.p, 4 * (size_t)m);
-  if (m > 0 && witness_out) h->d2h(witness_out, h->d_wit.p, (size_t)m);
-  h->sync();
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_event_received(hge_engine* h, int32_t* rr_out, int64_t* cts_out, int64_t cap) {
-  GUARD_BEGIN
-  const int64_t m = std::min<int64_t>(cap, h->n_events);
-  if (m > 0 && rr_out) h->d2h(rr_out, h->d_rr.p, 4 * (size_t)m);
-  if (m > 0 && cts_out) h->d2h(cts_out, h->d_cts.p, 8 * (size_t)m);
-  h->sync();
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_consensus_timestamp_sources(hge_engine* h, const int32_t* ids, int64_t n, int32_t* src_out) {
-  if (!h || n < 0 || (n > 0 && (!ids || !src_out))) return HGE_ERR_ARG;
-  GUARD_BEGIN
-  if (n == 0) return HGE_OK;
-  for (int64_t i = 0; i < n; i++)
-    if (ids[i] < 0 || ids[i] >= h->n_events) throw Error(HGE_ERR_ARG, "hge_consensus_timestamp_sources: unknown id");
-  h->s_src.need((size_t)n * 2);
-  h->h2d(h->s_src.p, ids, 4 * (size_t)n);
-  hipLaunchKernelGGL(k_cts_source, dim3((unsigned)div_up(n, 4)), dim3(256), 0, h->st, h->tables(),
-                     (const int32_t*)h->s_src.p, (int)n, (const int32_t*)h->d_rr.p, (const int64_t*)h->d_cts.p,
-                     h->s_src.p + n);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) throw Error(HGE_ERR_DEVICE, std::string("launch k_cts_source: ") + hipGetErrorString(le));
-  h->readback(src_out, h->s_src.p + n, (size_t)n);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int32_t hge_fame_table(hge_engine* h, int32_t rounds, int8_t* fame_out) {
-  if (!h) return HGE_ERR_ARG;
-  GUARD_BEGIN
-  const int R = std::min<int>(std::max(rounds, 0), std::min(h->R, h->Rcap));
-  if (R == 0 || !fame_out) return 0;
-  const size_t n = (size_t)R * h->N;
-  std::vector<int32_t> w(n);
-  std::vector<uint8_t> f(n);
-  h->d2h(w.data(), h->d_W.p, 4 * n);
-  h->d2h(f.data(), h->d_fame.p, n);
-  h->sync();
-  for (size_t i = 0; i < n; i++)
-    fame_out[i] = (w[i] >= 0 && w[i] < h->n_divided) ? (int8_t)f[i] : (int8_t)-1;
-  return R;
-  GUARD_END(h)
-}
-
-// ---- round predicates (hashgraph.go:211-326) --------------------------------
-int32_t hge_parent_round(hge_engine* h, int32_t x) {
-  if (x < 0 || x >= h->n_events) return -1;
-  const int32_t sp = h->h_sp[x], op = h->h_op[x];
-  if (sp < 0 && op < 0) return 0;
-  if (sp < 0 || op < 0) return 0;  // a missing parent (GetEvent error) reads as 0
-  const int32_t a = hge_round_of(h, sp), b = hge_round_of(h, op);
-  return std::max(a, b);
-}
-
-int32_t hge_round_inc(hge_engine* h, int32_t x) {
-  if (x < 0 || x >= h->n_events) return 0;
-  const int32_t pr = hge_parent_round(h, x);
-  if (pr < 0 || hge_rounds(h) < pr + 1) return 0;
-  try {
-    h->coords();
-    if (pr >= h->Rcap) return 0;
-    std::vector<int32_t> w(h->N);
-    h->readback(w.data(), h->d_W.p + (size_t)pr * h->N, h->N);
-    int c = 0;
-    for (int i = 0; i < h->N; i++)
-      if (w[i] >= 0 && w[i] < h->n_events) c += hge_strongly_see(h, x, w[i]);
-    return c >= h->SM ? 1 : 0;
-  } catch (Error& e) {
-    h->err = e.msg;
-    return 0;
-  }
-}
-
-int hge_round_diff(hge_engine* h, int32_t x, int32_t y, int32_t* out) {
-  if (x < 0 || x >= h->n_events || y < 0 || y >= h->n_events || !out) return HGE_ERR_ARG;
-  const int32_t a = hge_round_of(h, x), b = hge_round_of(h, y);
-  if (a < 0 || b < 0) return HGE_ERR_INTERNAL;
-  *out = a - b;
-  return HGE_OK;
-}
-
-int hge_set_round(hge_engine* h, int32_t round, const int32_t* ids, const uint8_t* witness,
-                  const uint8_t* fame, int32_t n) {
-  GUARD_BEGIN
-  if (round < 0 || n < 0 || (n > 0 && !ids)) return HGE_ERR_ARG;
-  h->coords();
-  h->ensure_rcap((int64_t)round + 1);
-  for (int32_t i = 0; i < n; i++) {
-    const int32_t x = ids[i];
-    if (x < 0 || x >= h->n_events) return HGE_ERR_ARG;
-    if (witness && !witness[i]) continue;
-    const size_t slot = (size_t)round * h->N + h->h_creator[x];
-    h->h2d(h->d_W.p + slot, &ids[i], 4);
-    const uint8_t f = fame ? fame[i] : 0;
-    h->h2d(h->d_fame.p + slot, &f, 1);
-    h->sync();
-  }
-  h->R_set = std::max(h->R_set, round + 1);
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_set_profiling(hge_engine* h, int on) {
-  h->prof_on = on != 0;
-  return HGE_OK;
-}
-
-int hge_reset_kernel_stats(hge_engine* h) {
-  h->prof_names.clear();
-  h->prof_ms.clear();
-  h->prof_cnt.clear();
-  return HGE_OK;
-}
-
-int hge_kernel_stats(hge_engine* h, int k, char* name, int namecap, double* total_ms,
-                     int64_t* launches) {
-  const int n = (int)h->prof_names.size();
-  if (k < 0 || k >= n) return n;
-  if (name && namecap > 0) {
-    snprintf(name, namecap, "%s", h->prof_names[k].c_str());
-  }
-  if (total_ms) *total_ms = h->prof_ms[k];
-  if (launches) *launches = h->prof_cnt[k];
-  return n;
-}
-
-int32_t hge_coordinate_sweeps(hge_engine* h) { return h ? h->n_sweeps : -1; }
-
-int hge_walk_select_paths(hge_engine* h, int64_t* narrow, int64_t* exact) {
-  GUARD_BEGIN
-  unsigned long long v[2] = {0, 0};
-  if (h->s_wpaths.p && h->walk_seq > 0) {
-    h->d2h(v, h->s_wpaths.p + 2 * (h->walk_seq & 1), 16);
-    h->sync();
-  }
-  if (narrow) *narrow = (int64_t)v[0];
-  if (exact) *exact = (int64_t)v[1];
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int hge_sort_paths(hge_engine* h, int64_t* packed, int64_t* index) {
-  GUARD_BEGIN
-  unsigned long long v[2] = {0, 0};
-  if (h->s_spaths.p && h->sort_counted) {
-    h->d2h(v, h->s_spaths.p + 4 * (h->sort_seq & 1), 16);
-    h->sync();
-  }
-  if (packed) *packed = (int64_t)v[0];
-  if (index) *index = (int64_t)v[1];
-  return HGE_OK;
-  GUARD_END(h)
-}
-
-int64_t hge_host_syncs(hge_engine* h) { return h ? h->n_syncs : -1; }
-
-int hge_stage_times(hge_engine* h, float* ms_out, int cap) {
-  int n = std::min(cap, 7);
-  for (int i = 0; i < n; i++) ms_out[i] = h->stage_ms[i];
-  return n;
-}
-
-int64_t hge_frontier_fallbacks(hge_engine* h) {
-  if (!h) return HGE_ERR_ARG;
-  return h->n_frontier_fallbacks;
-}
-
-}  // extern "C"
+#include "hge_engine_abi.hip"

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hge_hostlog.h"
 #include "hge_sortkey.h"
 
 #define INF32 0x7FFFFFFF
@@ -262,13 +263,7 @@ __global__ void k_scan_add(int32_t* out, int n, const int32_t* partial_scanned) 
   if (i < n) out[i] += partial_scanned[i / 1024];
 }
 
-// A small batch's event fields uploaded as one packed record per event (one copy
-// instead of eight; hge_engine.hip upload()), unpacked by k_chain_fill.
-struct UpEv {
-  int32_t creator, index, sp, op, ntx, coin;
-  int64_t ts;
-  uint64_t S[4];
-};
+// where k_chain_fill unpacks a small batch's packed records (UpEv, hge_hostlog.h)
 struct UpDst {
   int32_t *creator, *index, *sp, *op, *ntx;
   int64_t* ts;

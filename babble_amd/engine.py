@@ -539,6 +539,10 @@ class Engine:
         except Exception:
             pass
 
+    def reset(self):
+        """hge_reset: an empty stream on the same engine (its tables and buffers stay)."""
+        self._check(self.L.hge_reset(self.h))
+
     def _check(self, rc):
         if rc != 0:
             xe, self._xerr = getattr(self, "_xerr", None), None
