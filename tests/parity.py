@@ -68,9 +68,22 @@ def with_creators(eng, dag, status):
     return eng
 
 
-def run_case(eng, dag, k, check_events=True):
+def oracle_reach(dag, o, ost, oorder, ocounts):
+    """ts_shapes.reach() of an oracle run (what the stream's timestamps put the median
+    and the sort through)."""
+    from ts_shapes import reach
+    rr, cts = o.event_received()
+    return reach(dag, dict(status=ost, order=oorder, counts=ocounts, rr=rr, cts=cts))
+
+
+def run_case(eng, dag, k, check_events=True, expect=None, scale=False):
+    """expect(reach): called with oracle_reach() of the oracle's run before the engine
+    replays, to assert that the stream reaches what the test is about.  scale: the
+    oracle's scale mode (the same results, test_oracle_scale.py; seconds less at N = 256)."""
     calls = schedule(len(dag["creator"]), k)
-    o, ost, oorder, ocounts = oracle_run(dag, calls)
+    o, ost, oorder, ocounts = oracle_replay(dag, calls, 0, scale=scale)
+    if expect is not None:
+        expect(oracle_reach(dag, o, ost, oorder, ocounts))
     st, order, counts = eng.replay(dag, calls)
     with_creators(eng, dag, st)
     np.testing.assert_array_equal(st, ost, err_msg="admission status differs")

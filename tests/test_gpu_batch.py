@@ -11,7 +11,17 @@ chain's head (op_lag), coin rounds (one call over the whole stream at N = 4, 32 
 64, the widest; at N = 4, 5 and 8 with coin-bit votes taken: COIN_CASES), and a second
 run of the same batch.  The call schedule runs in bulk (hge_batch_bulk.hip); a graph past
 the bulk fold's 256 rounds is replayed call by call by kb_consensus in the same
-run, and HGB_SERIAL=1 puts every graph through kb_consensus."""
+run, and HGB_SERIAL=1 puts every graph through kb_consensus.
+
+Every stream here keeps random_gossip's own timestamps (1 us apart, in submission order)
+and uniform S.  The timestamps of real clocks are test_gpu_batch_timestamps.py's, on the
+shapes of ts_shapes.py at N = 4, 5, 32, 33 and 64, in bulk, under HGB_SERIAL=1 and with the
+commit records delivered: median offsets outside int32 and on +-INT32_MAX (kb_median's
+exact rank search, kb_consensus's twin of it, the register sort's filler value), call
+buckets whose timestamps span 2^28 ns or more (kb_sort unpacked, every comparison from
+HBM) or one less (the packed field's top bit), and keys equal down to S's last limb
+(key_less past the first limb in every sort).  One branch no stream reaches: a call
+bucket received over 16 rounds or more, the other half of kb_sort's packing condition."""
 import os
 import sys
 

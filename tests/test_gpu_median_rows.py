@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from babble_amd.gossip import random_gossip, schedule
-from parity import compare_state, oracle_run, with_creators
+from parity import compare_state, oracle_reach, oracle_run, with_creators
+from ts_shapes import shape
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +34,8 @@ def _stream(kind):
         dag["ts"] = 1_700_000_000_000_000_000 + rng.integers(-(1 << 30) + 1, 1 << 30, E, dtype=np.int64)
     elif kind == "ties":
         dag["ts"] = 1_700_000_000_000_000_000 + (ids // 97) * 1000
+    elif kind in ("two31m", "two31"):  # every offset 0 or +-(2^31 - 1), the last of the int32 rows; or +-2^31
+        dag = shape(dag, kind, SEED)
     else:
         assert kind == "plain"
     return dag
@@ -48,6 +51,9 @@ def _reference(kind):
         calls = schedule(E, K)
         o, ost, oorder, ocounts = oracle_run(dag, calls)
         assert len(oorder) >= MIN_ORDERED, len(oorder)
+        if kind in ("two31m", "two31"):  # the oracle's own run shows events on / past the int32 edge
+            r = oracle_reach(dag, o, ost, oorder, ocounts)
+            assert (r["edge_i32"] > 0 and r["out_i32"] == 0) if kind == "two31m" else r["out_i32"] > 0, r
         _refs[kind] = (dag, calls, o, ost, oorder, ocounts)
     return _refs[kind]
 
@@ -67,11 +73,13 @@ def _check_replay(eng, kind):
     compare_state(eng, o)
 
 
-@pytest.mark.parametrize("kind", ["plain", "wide", "spread", "ties"])
+@pytest.mark.parametrize("kind", ["plain", "wide", "spread", "ties", "two31m", "two31"])
 def test_median_rows_parity(kind):
     """Full state against the oracle at N = 132: the plain stream; timestamps that grow by
     3 s per 500 events (offsets outside int32: the wide rows of the uint16 path);
-    timestamps spread over +-2^30 ns; long runs of equal timestamps."""
+    timestamps spread over +-2^30 ns; long runs of equal timestamps; two timestamps
+    2^31 - 1 ns apart (offsets of +-INT32_MAX, the last that stay int32 rows, their image
+    the select's filler) and 2^31 ns apart (the first that must not)."""
     from babble_amd.engine import Engine
     eng = Engine(N, E)
     try:

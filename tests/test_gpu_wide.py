@@ -5,6 +5,7 @@ import pytest
 
 from babble_amd.gossip import random_gossip
 from parity import run_case
+from ts_shapes import shape
 
 pytestmark = pytest.mark.gpu
 
@@ -145,24 +146,47 @@ def test_timestamp_offsets_outside_int32(n, events):
         eng.close()
 
 
+def _on_the_edge(r):
+    assert r["edge_i32"] > 0 and r["out_i32"] == 0, r
+
+
+def _past_the_edge(r):
+    assert r["out_i32"] > 0, r
+
+
 @pytest.mark.parametrize("n,events,kind", [(64, 5000, "spread"), (256, 3000, "spread"),
-                                           (64, 5000, "ties"), (128, 4000, "ties")])
+                                           (64, 5000, "ties"), (128, 4000, "ties"),
+                                           (16, 3000, "two31m"), (64, 5000, "two31m"), (256, 11000, "two31m"),
+                                           (16, 3000, "two31"), (64, 5000, "two31"), (256, 11000, "two31")])
 def test_median_select_extremes(n, events, kind):
     """The 32-bit select on timestamp offsets at its edges: timestamps out of order
     and spread over +-2^30 ns (offsets up to +-(2^31 - 2): spans close to 2^32, the
     order-preserving images near 1 and 2^32 - 1), and long runs of equal timestamps
     (ties: the select runs every bit without isolating a single value).  Consensus
-    timestamps and order vs the oracle (MedianTimestamp, hashgraph.go:762-770)."""
+    timestamps and order vs the oracle (MedianTimestamp, hashgraph.go:762-770).
+
+    two31m / two31 (tests/ts_shapes.py): two timestamps 2^31 - 1 or 2^31 ns apart, so every
+    offset is 0 or exactly that.  +-INT32_MAX is the last offset of the int32 path, where
+    its image equals the select's filler (~0u) and sits one off the transpose's escape mark
+    (INT32_MIN); +-2^31 is the first that must take the exact 64-bit path.  At N = 16 (the
+    N <= 32 path), 64 (k_median_wave behind k_fd_transpose_ts) and 256 (the widest); the
+    oracle's own run must show such events before anything is compared.  At N = 256 that
+    takes 11,000 events: a 256-wide stream of 3,000 (the `spread` case above) or of 10,000
+    never leaves its third round and orders nothing, so no median is taken at all."""
     from babble_amd.engine import Engine
     dag = random_gossip(n, events, seed=300 + n)
+    expect = None
     if kind == "spread":
         rng = np.random.default_rng(n)
         dag["ts"] = 1_700_000_000_000_000_000 + rng.integers(-(1 << 30) + 1, 1 << 30, events, dtype=np.int64)
-    else:
+    elif kind == "ties":
         dag["ts"] = 1_700_000_000_000_000_000 + (np.arange(events, dtype=np.int64) // 97) * 1000
+    else:
+        dag = shape(dag, kind, 300 + n)
+        expect = _on_the_edge if kind == "two31m" else _past_the_edge
     eng = Engine(n, 1 << 14)
     try:
-        run_case(eng, dag, n)
+        run_case(eng, dag, n, expect=expect, scale=events > 10000)
     finally:
         eng.close()
 
