@@ -39,6 +39,7 @@
 #include "hge_rounds_coop.hip"
 #include "hge_rounds_direct.hip"
 #include "hge_walk_spec.hip"
+#include "hge_commit.hip"
 
 using namespace hge;
 
@@ -196,6 +197,9 @@ struct hge_engine {
   // coordinate sweeps: scratch
   DBuf<int32_t> s_chg, s_bar, s_dirty;
   DBuf<int32_t> s_src;  // hge_consensus_timestamp_sources: ids, then their sources
+  // hge_commit_records: one chunk's consensus timestamps, then (as int32) its ids, rounds
+  // received and sources; sized by the chunk, not by the log
+  DBuf<int64_t> s_rec;
   // windowed lastAncestors (hge_coords_win.hip): chunk plans, row sums, starting rows
   DBuf<int4> s_lwplan;
   DBuf<uint32_t> s_lwsum, s_lwinit;
@@ -2297,6 +2301,70 @@ struct hge_engine {
   void commit_lcr(int lcr_new, int lcr_events) {
     cons.lcr = lcr_new;
     cons.lcre = lcr_new - 1 >= 0 ? lcr_events : 0;
+  }
+
+  // hge_commit_records: entries [from, from + m) of the log (the vector, then the tail a
+  // replay left in the pinned order buffer) as records, a read of persisted state
+  // (hge_commit.hip).  Chunks of at most kRecordsChunk records, each one launch and one
+  // wait: the device scratch and the arena's pieces are a chunk's, whatever the log's length.
+  // A chunk's ids from the vector go up through the arena; the pinned tail is copied from
+  // where it lies.  Nothing runs on the device for the ids alone.
+  static constexpr int64_t kRecordsChunk = 1 << 20;
+  void commit_records(int64_t from, int64_t m, int32_t* ids_out, int32_t* rr_out, int64_t* cts_out, int32_t* src_out) {
+    const int64_t V = (int64_t)cons.consensus.size();
+    auto host_ids = [&](int64_t a, int64_t k, auto&& piece) {  // [a, a + k) as its (at most two) pieces
+      const int64_t kv = std::max<int64_t>(0, std::min(a + k, V) - a);
+      if (kv > 0) piece((int64_t)0, cons.consensus.data() + a, kv, false);
+      if (k > kv) piece(kv, (const int32_t*)pin_ord.p + (a + kv - V), k - kv, true);
+    };
+    if (ids_out)
+      host_ids(from, m, [&](int64_t at, const int32_t* p, int64_t k, bool) { memcpy(ids_out + at, p, 4 * (size_t)k); });
+    if (!rr_out && !cts_out && !src_out) return;
+    const int64_t CH = hge_hooks::test_records_chunk(kRecordsChunk);
+    for (int64_t a = from; a < from + m; a += CH) {
+      const int k = (int)std::min<int64_t>(CH, from + m - a);
+      s_rec.need(3 * (size_t)k);  // cts[k] | ids[k] rr[k] | src[k] ...
+      int64_t* const d_c = s_rec.p;
+      int32_t* const d_i = (int32_t*)(s_rec.p + k);
+      int32_t *const d_r = d_i + k, *const d_s = d_i + 2 * (size_t)k;
+      // the chunk's pieces of the arena in one go: no drain between them (a call's records
+      // cost one host wait)
+      xfer.reserve(((4 * (size_t)k + 255) & ~(size_t)255) * (1 + (rr_out ? 1 : 0) + (src_out ? 1 : 0)) +
+                   (cts_out ? (8 * (size_t)k + 255) & ~(size_t)255 : 0));
+      host_ids(a, k, [&](int64_t at, const int32_t* p, int64_t kk, bool pinned) {
+        if (pinned) {  // (already pinned: the copy waits for nothing)
+          hp.copies++;
+          HGE_HIPCHK(hipMemcpyAsync(d_i + at, p, 4 * (size_t)kk, hipMemcpyHostToDevice, st));
+        } else {
+          h2d(d_i + at, p, 4 * (size_t)kk);
+        }
+      });
+      int32_t* const rr_o = rr_out ? d_r : nullptr;
+      int64_t* const cts_o = cts_out ? d_c : nullptr;
+      if (!src_out) {
+        KLAUNCH(k_commit_records_plain, dim3((unsigned)div_up(k, 256)), dim3(256), 0, st, (const int32_t*)d_i, k,
+                (const int32_t*)d_rr.p, (const int64_t*)d_cts.p, rr_o, cts_o);
+      } else {
+#define HGE_RECORDS(G)                                                                                        \
+  KLAUNCH(k_commit_records<G>, dim3((unsigned)div_up(k, 256 / G)), dim3(256), 0, st, tables(), (const int32_t*)d_i, k, \
+          (const int32_t*)d_rr.p, (const int64_t*)d_cts.p, rr_o, cts_o, d_s)
+        // a record's lane group: min(64, the next power of two >= N)
+        if (N > 32) HGE_RECORDS(64);
+        else if (N > 16) HGE_RECORDS(32);
+        else if (N > 8) HGE_RECORDS(16);
+        else if (N > 4) HGE_RECORDS(8);
+        else if (N > 2) HGE_RECORDS(4);
+        else if (N > 1) HGE_RECORDS(2);
+        else HGE_RECORDS(1);
+#undef HGE_RECORDS
+      }
+      const int64_t o = a - from;
+      if (rr_out) d2h(rr_out + o, d_r, 4 * (size_t)k);
+      if (cts_out) d2h(cts_out + o, d_c, 8 * (size_t)k);
+      if (src_out) d2h(src_out + o, d_s, 4 * (size_t)k);
+      sync();
+    }
+    prof.collect();
   }
 
   // the batch's one closing round trip (read in place from the pinned arena); a

@@ -804,6 +804,54 @@ int hge_consensus_timestamp_sources(hge_engine* h, const int32_t* ids, int64_t n
   GUARD_END(h)
 }
 
+// FindOrder's records of the log range [from, from + cap) (hashgraph.go:723-760), read from
+// persisted state (hge_engine::commit_records).  The log is not folded into its vector for
+// this: a replay's tail is read where hge_replay_run delivered it.
+int64_t hge_commit_records(hge_engine* h, int64_t from, int64_t cap, int32_t* ids_out, int32_t* rr_out,
+                           int64_t* cts_out, int32_t* src_out) {
+  if (!h) return HGE_ERR_ARG;
+  GUARD_BEGIN
+  if (from < 0 || cap < 0) throw Error(HGE_ERR_ARG, "hge_commit_records: negative range");
+  const int64_t left = std::max<int64_t>(0, h->consensus_size() - from);
+  const int64_t m = std::min(cap, left);
+  if (m > 0) h->commit_records(from, m, ids_out, rr_out, cts_out, src_out);
+  return left;
+  GUARD_END(h)
+}
+
+// the batch an order call just committed (the log's last n entries) as records
+static void batch_records(hge_engine* h, int64_t n, int64_t cap, int32_t* ids_out, int32_t* rr_out, int64_t* cts_out,
+                          int32_t* src_out) {
+  const int64_t m = std::min(std::max<int64_t>(cap, 0), n);
+  if (m > 0) h->commit_records(h->consensus_size() - n, m, ids_out, rr_out, cts_out, src_out);
+}
+
+int hge_find_order_records(hge_engine* h, int64_t cap, int32_t* ids_out, int32_t* rr_out, int64_t* cts_out,
+                           int32_t* src_out, int64_t* n_out) {
+  if (!h) return HGE_ERR_ARG;
+  int64_t n = 0;
+  const int rc = hge_find_order(h, nullptr, 0, &n);
+  if (rc != HGE_OK) return rc;
+  GUARD_BEGIN
+  batch_records(h, n, cap, ids_out, rr_out, cts_out, src_out);
+  if (n_out) *n_out = n;
+  return HGE_OK;
+  GUARD_END(h)
+}
+
+int hge_run_consensus_records(hge_engine* h, int64_t cap, int32_t* ids_out, int32_t* rr_out, int64_t* cts_out,
+                              int32_t* src_out, int64_t* n_out) {
+  if (!h) return HGE_ERR_ARG;
+  int64_t n = 0;
+  const int rc = hge_run_consensus(h, nullptr, 0, &n);
+  if (rc != HGE_OK) return rc;
+  GUARD_BEGIN
+  batch_records(h, n, cap, ids_out, rr_out, cts_out, src_out);
+  if (n_out) *n_out = n;
+  return HGE_OK;
+  GUARD_END(h)
+}
+
 int32_t hge_fame_table(hge_engine* h, int32_t rounds, int8_t* fame_out) {
   if (!h) return HGE_ERR_ARG;
   GUARD_BEGIN

@@ -59,5 +59,7 @@ inline int test_handoff_stall() { return num("HGE_TEST_HANDOFF_STALL", 0); }
 inline bool test_handoff_fail() { return is_set("HGE_TEST_HANDOFF_FAIL"); }
 // HGE_TEST_SORT_INDEX=1: every bucket of the order stage takes the index sort.  Per use.
 inline int test_sort_index() { return nonzero("HGE_TEST_SORT_INDEX") ? 1 : 0; }
+// HGE_TEST_RECORDS_CHUNK=k: hge_commit_records works in chunks of k (at least 1, at most `chunk`) records (tests: several chunks at test sizes).  Per use.
+inline long long test_records_chunk(long long chunk) { return is_set("HGE_TEST_RECORDS_CHUNK") ? std::max<long long>(1, std::min<long long>(chunk, num("HGE_TEST_RECORDS_CHUNK", 0))) : chunk; }
 
 }  // namespace hge_hooks

@@ -54,6 +54,13 @@ struct Xfer {
     pin_used += need;
     return q;
   }
+  // room for pieces of `bytes` in all (each rounded up by its caller) without a drain
+  // between them: an idle arena is regrown as it is, a used one is drained first
+  void reserve(size_t bytes) {
+    if (pin_used + bytes <= pin.n) return;
+    if (pin_used || !pending.empty()) sync();
+    if (bytes > pin.n) pin.need(std::max<size_t>(bytes, std::max<size_t>(2 * pin.n, 1 << 16)));
+  }
   void h2d(void* dev, const void* host, size_t bytes) {
     if (!bytes) return;
     char* q = pin_take(bytes);

@@ -72,6 +72,7 @@ EXPORTS = [
     "hge_undetermined", "hge_known", "hge_round_of", "hge_is_witness", "hge_round_witness",
     "hge_fame", "hge_round_events", "hge_round_received", "hge_consensus_timestamp",
     "hge_consensus_timestamp_sources",
+    "hge_commit_records", "hge_find_order_records", "hge_run_consensus_records",
     "hge_ancestor", "hge_self_ancestor", "hge_see", "hge_strongly_see",
     "hge_oldest_self_ancestor_to_see", "hge_coordinates", "hge_coordinate_sweeps", "hge_walk_select_paths", "hge_sort_paths", "hge_host_syncs", "hge_frontier_fallbacks",
     "hge_stage_times",
@@ -207,6 +208,11 @@ def lib():
     L.hge_event_rounds.argtypes = [vp, P(i32), P(ctypes.c_uint8), i64]
     L.hge_event_received.argtypes = [vp, P(i32), P(i64), i64]
     L.hge_consensus_timestamp_sources.argtypes = [vp, P(i32), i64, P(i32)]
+    if hasattr(L, "hge_commit_records"):  # (a build of an older tree, HGE_LIB, lacks them)
+        L.hge_commit_records.argtypes = [vp, i64, i64, P(i32), P(i32), P(i64), P(i32)]
+        L.hge_commit_records.restype = i64
+        for f in ("hge_find_order_records", "hge_run_consensus_records"):
+            getattr(L, f).argtypes = [vp, i64, P(i32), P(i32), P(i64), P(i32), P(i64)]
     L.hge_fame_table.argtypes = [vp, i32, P(ctypes.c_int8)]
     L.hge_fame_table.restype = i32
     L.hge_set_cache_size.argtypes = [vp, i64]
@@ -643,6 +649,43 @@ class Engine:
     def run_consensus(self):
         return self._order_call(self.L.hge_run_consensus)
 
+    def _records_call(self, fn, sources):
+        # a call orders undetermined events only: their count (after the inserts) bounds the batch
+        cap = max(1, int(self.L.hge_event_count(self.h)))
+        ids, rr, cts = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int64)
+        src = np.empty(cap, np.int32) if sources else None
+        n = ctypes.c_int64()
+        self._check(fn(self.h, cap, _p32(ids), _p32(rr), _p64(cts), _p32(src) if sources else None, ctypes.byref(n)))
+        m = n.value
+        return dict(ids=ids[:m].copy(), rr=rr[:m].copy(), cts=cts[:m].copy(), src=src[:m].copy() if sources else None)
+
+    def find_order_records(self, sources=True):
+        """find_order() with the call's batch as FindOrder hands it over (hge_find_order_records):
+        dict(ids, rr, cts, src), see commit_records()."""
+        return self._records_call(self.L.hge_find_order_records, sources)
+
+    def run_consensus_records(self, sources=True):
+        """run_consensus() with the call's batch as records (hge_run_consensus_records)."""
+        return self._records_call(self.L.hge_run_consensus_records, sources)
+
+    def commit_records(self, start=0, stop=None, sources=True):
+        """Entries [start, stop) of the commit log (stop None: to its end) as FindOrder hands
+        them to its caller (hge_commit_records): dict(ids, rr, cts, src) of arrays in log order,
+        the event, its round received, its consensus timestamp and the event whose own
+        timestamp that is (src is None with sources=False: the source search does not run)."""
+        start = int(start)
+        left = self.L.hge_commit_records(self.h, start, 0, None, None, None, None)
+        if left < 0:
+            raise HgeError(left, self.L.hge_last_error(self.h).decode())
+        m = left if stop is None else max(0, min(left, int(stop) - start))
+        ids, rr, cts = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int64)
+        src = np.zeros(max(m, 1), np.int32) if sources else None
+        got = self.L.hge_commit_records(self.h, start, m, _p32(ids), _p32(rr), _p64(cts),
+                                        _p32(src) if sources else None)
+        if got < 0:
+            raise HgeError(got, self.L.hge_last_error(self.h).decode())
+        return dict(ids=ids[:m], rr=rr[:m], cts=cts[:m], src=src[:m] if sources else None)
+
     def replay(self, dag_or_events, call_points):
         ev = dag_or_events if isinstance(dag_or_events, np.ndarray) else events_array(dag_or_events)
         self.prepare(ev, call_points)
@@ -667,13 +710,15 @@ class Engine:
 
     def order_view(self):
         """The replay's order where hge_replay_run delivered it (pinned host memory), as a
-        numpy view without a copy: valid until the next replay or consensus call."""
+        read-only numpy view without a copy: valid until the next replay or consensus call.
+        The array keeps a reference to the Engine, so dropping the Engine while holding the
+        view does not free the memory under it."""
         p = ctypes.POINTER(ctypes.c_int32)()
         n = ctypes.c_int64()
         self._check(self.L.hge_replay_order(self.h, ctypes.byref(p), ctypes.byref(n)))
         if n.value == 0:
             return np.zeros(0, np.int32)
-        return np.ctypeslib.as_array(p, shape=(n.value,))
+        return np.asarray(_HostView(self, p, n.value, "<i4"))
 
     def fetch(self):
         order = np.zeros(max(1, self._nordered), np.int32)

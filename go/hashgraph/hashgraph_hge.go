@@ -402,38 +402,34 @@ func (h *Hashgraph) DecideRoundReceived() error {
 // FindOrder (hashgraph.go:723-760): the engine commits this call's batch in
 // consensus order; the shim maps ids back to Events and sends on commitCh.
 func (h *Hashgraph) FindOrder() error {
+	// one call: the batch comes back as FindOrder hands it over (id, round received,
+	// MedianTimestamp's source).  A call orders undetermined events only, so their count
+	// bounds the batch.
+	bound := C.hge_undetermined(h.eng, nil, 0)
+	ids := make([]C.int32_t, int(bound)+1)
+	rrs := make([]C.int32_t, int(bound)+1)
+	srcs := make([]C.int32_t, int(bound)+1)
 	var n C.int64_t
-	if C.hge_find_order(h.eng, nil, 0, &n) != C.HGE_OK { // size only: nothing is committed twice
+	if C.hge_find_order_records(h.eng, bound, &ids[0], &rrs[0], nil, &srcs[0], &n) != C.HGE_OK {
 		return h.engineErr()
 	}
-	// the batch is the tail of the consensus log
-	total := int64(C.hge_consensus_count(h.eng))
-	from := total - int64(n)
 	batch := make([]Event, 0, int(n))
-	if n > 0 {
-		ids := make([]C.int32_t, int(n))
-		srcs := make([]C.int32_t, int(n))
-		C.hge_consensus_log(h.eng, C.int64_t(from), &ids[0], n)
+	for q := 0; q < int(n); q++ {
+		hex := h.store.hash(ids[q])
+		ev, err := h.Store.GetEvent(hex)
+		if err != nil {
+			return err
+		}
 		// MedianTimestamp returns the source event's own Body.Timestamp
 		// (hashgraph.go:762-770): its location too, not only the instant
-		if C.hge_consensus_timestamp_sources(h.eng, &ids[0], n, &srcs[0]) != C.HGE_OK {
-			return h.engineErr()
+		src, err := h.Store.GetEvent(h.store.hash(srcs[q]))
+		if err != nil {
+			return err
 		}
-		for q, id := range ids {
-			hex := h.store.hash(id)
-			ev, err := h.Store.GetEvent(hex)
-			if err != nil {
-				return err
-			}
-			src, err := h.Store.GetEvent(h.store.hash(srcs[q]))
-			if err != nil {
-				return err
-			}
-			ev.SetRoundReceived(int(C.hge_round_received(h.eng, id)))
-			ev.consensusTimestamp = src.Body.Timestamp
-			h.store.events[hex] = ev
-			batch = append(batch, ev)
-		}
+		ev.SetRoundReceived(int(rrs[q]))
+		ev.consensusTimestamp = src.Body.Timestamp
+		h.store.events[hex] = ev
+		batch = append(batch, ev)
 	}
 	und := int64(C.hge_undetermined(h.eng, nil, 0))
 	h.UndeterminedEvents = h.UndeterminedEvents[:0]

@@ -372,6 +372,30 @@ int64_t hge_consensus_timestamp(hge_engine* h, int32_t id);
  * chosen (the reference's sort.Sort over a map-ordered list leaves it unspecified).
  * -1 for an id with no round received. */
 int hge_consensus_timestamp_sources(hge_engine* h, const int32_t* ids, int64_t n, int32_t* src_out);
+/* Entries [from, from+cap) of the commit log, what FindOrder hands its caller
+ * (hashgraph.go:723-760): id, round received, consensus timestamp and the event whose
+ * Body.Timestamp that timestamp is (hashgraph.go:762-770; the rule of
+ * hge_consensus_timestamp_sources).  Returns the number of log entries from `from` to the
+ * end of the log (as hge_consensus_log does) and fills min(cap, that) of each non-NULL
+ * array; a negative HGE_ERR_* on failure (from < 0, cap < 0 or a NULL handle: HGE_ERR_ARG).
+ * Any output array may be NULL; with src_out NULL the source search does not run, and for
+ * the ids alone nothing runs on the device.  A read of persisted state (per-event round
+ * received and timestamp; the fame of a round at or below LastConsensusRound is final), so
+ * a record read later equals the record at commit time: valid after online calls, after
+ * hge_replay_run (the log is not copied for it), after online calls that follow a replay,
+ * after hge_reset and a new stream, and on every rank after hge_split_run (each rank holds
+ * every ordered event's rows).  Works in chunks of about 1M records, one launch and one
+ * host wait each; device scratch and pinned staging are a chunk's, not the log's. */
+int64_t hge_commit_records(hge_engine* h, int64_t from, int64_t cap,
+                           int32_t* ids_out, int32_t* rr_out, int64_t* cts_out, int32_t* src_out);
+/* hge_find_order / hge_run_consensus, the call's batch returned as records: the same call,
+ * then the new tail of the log read as above (at most one host wait more).  The batch is
+ * committed whatever cap is and *n_out is its size; a caller with a short buffer gets the
+ * rest from hge_commit_records(from = hge_consensus_count - n). */
+int hge_find_order_records(hge_engine* h, int64_t cap, int32_t* ids_out, int32_t* rr_out,
+                           int64_t* cts_out, int32_t* src_out, int64_t* n_out);
+int hge_run_consensus_records(hge_engine* h, int64_t cap, int32_t* ids_out, int32_t* rr_out,
+                              int64_t* cts_out, int32_t* src_out, int64_t* n_out);
 
 /* Bulk reads for ids [0, min(cap, hge_event_count)): Round/Witness of every
  * event (DivideRounds state), and RoundReceived (-1 = nil) / consensus timestamp. */
