@@ -1455,6 +1455,7 @@ __global__ __launch_bounds__(256, OCC) void kb_consensus(BT t) {
 }
 
 #include "hge_batch_bulk.hip"
+#include "hge_batch_gen.hip"
 
 }  // namespace hgb
 
@@ -1569,6 +1570,17 @@ struct hge_batch {
   HostField<int64_t> h_octs, h_counts;
   DBuf<int32_t> d_orr;  // the copy path's device side of rr / cts (ids and counts: d_order, d_counts)
   DBuf<int64_t> d_octs;
+  // generated graphs (hge_batch_generate, hge_batch_gen.hip): their parameters, and on
+  // the device the submission -> id map, the sizes the counting walk found, the raw
+  // submission pools and the accepted events' steps.  A batch holds these or `gs`.
+  std::vector<GenG> gen;
+  std::vector<int32_t> h_gcnt;
+  int64_t Stot = 0;
+  DBuf<GenG> d_gg;
+  DBuf<int32_t> d_gmap, d_gcnt, d_scr, d_six, d_ssp, d_sop, d_sstep, d_sst, d_sacc, d_estep;
+  DBuf<hge_event> d_raw;
+
+  int graphs() const { return gen.empty() ? (int)gs.size() : (int)gen.size(); }
 
   // the stream drained before the members die
   ~hge_batch() {
@@ -1617,6 +1629,7 @@ struct hge_batch {
       if (cp[c] < 1 || cp[c] > n_sub || (c > 0 && cp[c] <= cp[c - 1]))
         throw Error{HGE_ERR_ARG, "hge_batch_add: call points must be strictly ascending within [1, n_sub]"};
     if (n_sub >= INT32_MAX / 2) throw Error{HGE_ERR_ARG, "hge_batch_add: stream too long for a batch graph"};
+    if (!gen.empty()) throw Error{HGE_ERR_ARG, "hge_batch_add: the batch holds generated graphs (hge_batch_clear first)"};
     gs.emplace_back();
     Graph& G = gs.back();
     G.chain.assign(N, {});
@@ -1669,6 +1682,10 @@ struct hge_batch {
       return;
     }
     HGE_HIPCHK(hipSetDevice(device));
+    if (!gen.empty()) {
+      stage_generated();
+      return;
+    }
     const int G = (int)gs.size();
     hd.assign(G, GDesc{});
     Etot = Ktot = Rtot = 0;
@@ -1742,6 +1759,178 @@ struct hge_batch {
     up(d_cg, cgv);
     d_gd.need(G);
     HGE_HIPCHK(hipMemcpyAsync(d_gd.p, hd.data(), sizeof(GDesc) * G, hipMemcpyHostToDevice, st));
+    need_tables(G);
+    HGE_HIPCHK(hipStreamSynchronize(st));
+    ensure_delivery();
+    staged = true;
+  }
+
+  void generate(const hge_gossip_params& p, int32_t n_graphs, uint64_t seed0) {
+    if (!gs.empty()) throw Error{HGE_ERR_ARG, "hge_batch_generate: the batch holds added graphs (hge_batch_clear first)"};
+    GenG q{};
+    q.tf = (uint64_t)(p.fork_p * 4294967296.0);
+    q.tc = (uint64_t)(p.cascade_p * 4294967296.0);
+    q.events = (int32_t)p.events;
+    q.k = std::min<int64_t>(p.k, 5 * p.events);  // past the stream's length: one call
+    q.forkers = p.forkers;
+    q.op_lag = p.op_lag;
+    for (int32_t i = 0; i < n_graphs; i++) {
+      q.seed = seed0 + (uint64_t)i;
+      gen.push_back(q);
+    }
+    staged = false;
+    ran = false;
+  }
+
+  void clear() {
+    gs.clear();
+    gen.clear();
+    hd.clear();
+    staged = false;
+    ran = false;
+    delivered = 0;
+    n_fallback = 0;
+  }
+
+  GenT gen_tables() const {
+    GenT t{};
+    t.N = N;
+    t.ccap = ccap;
+    t.gg = d_gg.p;
+    t.gd = d_gd.p;
+    t.map = d_gmap.p;
+    t.cnt = d_gcnt.p;
+    t.s_cr = d_scr.p;
+    t.s_ix = d_six.p;
+    t.s_sp = d_ssp.p;
+    t.s_op = d_sop.p;
+    t.s_step = d_sstep.p;
+    t.s_st = d_sst.p;
+    t.s_acc = d_sacc.p;
+    t.cr = d_cr.p;
+    t.ix = d_ix.p;
+    t.sp = d_sp.p;
+    t.op = d_op.p;
+    t.oc = d_oc.p;
+    t.ntx = d_ntx.p;
+    t.estep = d_estep.p;
+    t.clen = d_clen.p;
+    t.chain = d_chain.p;
+    t.ntxch = d_ntxch.p;
+    t.cg = d_cg.p;
+    t.ts = d_ts.p;
+    t.tsch = d_tsch.p;
+    t.calls = d_calls.p;
+    t.S = d_S.p;
+    t.Sch = d_Sch.p;
+    t.coin = d_coin.p;
+    return t;
+  }
+
+  // The generated graphs' staging: what stage() uploads, written by kernels.  The pools'
+  // offsets need every graph's submission, accepted and call counts and the longest
+  // chain: a counting instance of the walk finds them (the walk is deterministic), one
+  // readback of 16 bytes per graph brings them to the host, and the walk runs again
+  // into pools laid out exactly.  An upper bound instead (5 submissions a step, all
+  // accepted, one chain) would size the E x N and chain tables of every later stage
+  // five and N times too large.
+  void stage_generated() {
+    const int G = (int)gen.size();
+    int64_t mtot = 0;
+    for (GenG& q : gen) {
+      q.mo = mtot;
+      q.so = 0;
+      mtot += 5 * (int64_t)q.events;
+    }
+    d_gg.need(G);
+    d_gcnt.need((size_t)G * 4);
+    d_gmap.need((size_t)mtot);
+    HGE_HIPCHK(hipMemcpyAsync(d_gg.p, gen.data(), sizeof(GenG) * G, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(kg_walk<false>, dim3(G), dim3(64), 0, st, gen_tables());
+    HGE_HIPCHK(hipGetLastError());
+    h_gcnt.resize((size_t)G * 4);
+    HGE_HIPCHK(hipMemcpyAsync(h_gcnt.data(), d_gcnt.p, (size_t)G * 16, hipMemcpyDeviceToHost, st));
+    HGE_HIPCHK(hipStreamSynchronize(st));
+    hd.assign(G, GDesc{});
+    Etot = Ktot = Rtot = Stot = 0;
+    ccap = 1;
+    Emax = 0;
+    int Kmax = 0;
+    for (int g = 0; g < G; g++) {
+      const int64_t nsub = h_gcnt[(size_t)g * 4], k = gen[g].k;
+      GDesc& d = hd[g];
+      d.eo = Etot;
+      d.E = h_gcnt[(size_t)g * 4 + 1];
+      d.co = (int32_t)Ktot;
+      d.K = (int32_t)((nsub + k - 1) / k);
+      d.ro = (int32_t)Rtot;
+      d.Rcap = d.E / SM + 2;
+      gen[g].so = Stot;
+      Etot += d.E;
+      Ktot += d.K;
+      Rtot += d.Rcap;
+      Stot += nsub;
+      ccap = std::max(ccap, (int)h_gcnt[(size_t)g * 4 + 2]);
+      Emax = std::max(Emax, d.E);
+      Kmax = std::max(Kmax, d.K);
+      if (Rtot >= INT32_MAX || Ktot >= INT32_MAX) throw Error{HGE_ERR_CAPACITY, "batch too large"};
+    }
+    HGE_HIPCHK(hipMemcpyAsync(d_gg.p, gen.data(), sizeof(GenG) * G, hipMemcpyHostToDevice, st));
+    d_gd.need(G);
+    HGE_HIPCHK(hipMemcpyAsync(d_gd.p, hd.data(), sizeof(GDesc) * G, hipMemcpyHostToDevice, st));
+    const size_t E1 = (size_t)std::max<int64_t>(Etot, 1), K1 = (size_t)std::max<int64_t>(Ktot, 1);
+    const size_t S1 = (size_t)std::max<int64_t>(Stot, 1), CH = (size_t)G * N * ccap;
+    for (DBuf<int32_t>* b : {&d_cr, &d_ix, &d_sp, &d_op, &d_oc, &d_ntx, &d_estep}) b->need(E1);
+    for (DBuf<int32_t>* b : {&d_scr, &d_six, &d_ssp, &d_sop, &d_sstep, &d_sst, &d_sacc}) b->need(S1);
+    d_ts.need(E1);
+    d_S.need(4 * E1);
+    d_coin.need(E1);
+    d_calls.need(K1);
+    d_cg.need(K1);
+    d_clen.need((size_t)G * N);
+    d_chain.need(CH);
+    d_tsch.need(CH);
+    d_Sch.need(CH);
+    d_ntxch.need(CH);
+    // the chain tables past a chain's length, as stage() uploads them
+    HGE_HIPCHK(hipMemsetAsync(d_chain.p, 0xFF, CH * 4, st));
+    HGE_HIPCHK(hipMemsetAsync(d_tsch.p, 0, CH * 8, st));
+    HGE_HIPCHK(hipMemsetAsync(d_Sch.p, 0, CH * 8, st));
+    HGE_HIPCHK(hipMemsetAsync(d_ntxch.p, 0, CH * 4, st));
+    const GenT t = gen_tables();
+    hipLaunchKernelGGL(kg_walk<true>, dim3(G), dim3(64), 0, st, t);
+    HGE_HIPCHK(hipGetLastError());
+    const int fx = (std::max(Emax, Kmax) + 255) / 256;
+    if (fx > 0) {
+      hipLaunchKernelGGL(kg_fill, dim3((unsigned)fx, (unsigned)G), dim3(256), 0, st, t);
+      HGE_HIPCHK(hipGetLastError());
+    }
+    need_tables(G);
+    HGE_HIPCHK(hipStreamSynchronize(st));
+    ensure_delivery();
+    staged = true;
+  }
+
+  // graph g's raw stream and admission results, read back from the staged pools
+  int64_t submissions(int32_t g, hge_event* ev_out, int32_t* status_out, int64_t cap) {
+    if (gen.empty() || !staged) throw Error{HGE_ERR_ARG, "hge_batch_submissions: no staged generated graphs"};
+    const int64_t nsub = h_gcnt[(size_t)g * 4];
+    if (cap < nsub || nsub == 0) return nsub;
+    HGE_HIPCHK(hipSetDevice(device));
+    if (ev_out) {
+      d_raw.need((size_t)nsub);
+      hipLaunchKernelGGL(kg_raw, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, gen_tables(), g, d_raw.p);
+      HGE_HIPCHK(hipGetLastError());
+      HGE_HIPCHK(hipMemcpyAsync(ev_out, d_raw.p, (size_t)nsub * sizeof(hge_event), hipMemcpyDeviceToHost, st));
+    }
+    if (status_out)
+      HGE_HIPCHK(hipMemcpyAsync(status_out, d_sst.p + gen[g].so, (size_t)nsub * 4, hipMemcpyDeviceToHost, st));
+    HGE_HIPCHK(hipStreamSynchronize(st));
+    return nsub;
+  }
+
+  // the tables a run writes, sized from the staged pools (hd, Etot, Ktot, Rtot, ccap)
+  void need_tables(int G) {
     const size_t E1 = (size_t)std::max<int64_t>(Etot, 1);
     d_LA.need(E1 * N);
     d_FDT.need((size_t)G * N * N * ccap);
@@ -1801,9 +1990,6 @@ struct hge_batch {
     d_wlc.need(1);
     d_gctx.need(G);
     d_cinf.need(E1);
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    ensure_delivery();
-    staged = true;
   }
 
   BT tables() const {
@@ -1958,7 +2144,7 @@ struct hge_batch {
   int64_t run() {
     stage();
     delivered = 0;
-    const int G = (int)gs.size();
+    const int G = graphs();
     if (G == 0) return 0;
     const size_t RN = (size_t)std::max<int64_t>(Rtot, 1) * N;
     const size_t E1 = (size_t)std::max<int64_t>(Etot, 1);
@@ -2132,24 +2318,24 @@ int hge_batch_run(hge_batch* b, int64_t* n_ordered) {
   BGUARD_END(b)
 }
 
-int32_t hge_batch_graphs(hge_batch* b) { return b ? (int32_t)b->gs.size() : -1; }
+int32_t hge_batch_graphs(hge_batch* b) { return b ? (int32_t)b->graphs() : -1; }
 
 int hge_batch_info(hge_batch* b, int32_t g, int64_t* info) {
-  if (!b || !info || g < 0 || g >= (int)b->gs.size()) return HGE_ERR_ARG;
+  if (!b || !info || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
   if (!b->ran) {
     b->err = "hge_batch_info: no replay yet (hge_batch_run)";
     return HGE_ERR_ARG;
   }
   const int64_t* s = &b->h_scal[(size_t)g * 8];
-  info[0] = (int64_t)b->gs[g].cr.size();
-  info[1] = (int64_t)b->gs[g].calls.size();
+  info[0] = b->hd[g].E;  // the staged graph's: generated graphs have no host mirror
+  info[1] = b->hd[g].K;
   for (int k = 0; k < 6; k++) info[2 + k] = s[k];
   return HGE_OK;
 }
 
 int hge_batch_results(hge_batch* b, int32_t g, int32_t* order, int64_t* counts, int32_t* round, uint8_t* witness,
                       int32_t* rr, int64_t* cts, int8_t* fame, int32_t* undetermined) {
-  if (!b || g < 0 || g >= (int)b->gs.size()) return HGE_ERR_ARG;
+  if (!b || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
   BGUARD_BEGIN
   if (!b->ran) throw Error{HGE_ERR_ARG, "hge_batch_results: no replay yet (hge_batch_run)"};
   const GDesc& d = b->hd[g];
@@ -2194,7 +2380,7 @@ int hge_batch_set_delivery(hge_batch* b, uint32_t what) {
 int32_t hge_batch_delivery(hge_batch* b) { return b && b->ran ? b->delivered : 0; }
 
 int hge_batch_commits_view(hge_batch* b, int32_t g, hge_batch_commits* out) {
-  if (!b || !out || g < 0 || g >= (int)b->gs.size()) return HGE_ERR_ARG;
+  if (!b || !out || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
   if (!b->ran || !b->delivered) {
     b->err = "hge_batch_commits_view: the last run did not deliver (hge_batch_set_delivery, then hge_batch_run)";
     return HGE_ERR_ARG;
@@ -2210,6 +2396,41 @@ int hge_batch_commits_view(hge_batch* b, int32_t g, hge_batch_commits* out) {
   return HGE_OK;
 }
 
+int hge_gossip_params_check(int32_t n_participants, const hge_gossip_params* p, int32_t n_graphs) {
+  if (!p || n_participants < 1 || n_participants > 64 || n_graphs < 1) return HGE_ERR_ARG;
+  if (p->events < n_participants || p->events > HGE_GOSSIP_MAX_EVENTS || p->forkers < 0 || p->k < 1) return HGE_ERR_ARG;
+  if (!(p->fork_p >= 0.0 && p->fork_p <= 1.0) || !(p->cascade_p >= 0.0 && p->cascade_p <= 1.0)) return HGE_ERR_ARG;
+  if (p->op_lag < 0 || p->op_lag > HGE_GOSSIP_MAX_OP_LAG) return HGE_ERR_ARG;
+  return HGE_OK;
+}
+
+int hge_batch_generate(hge_batch* b, const hge_gossip_params* p, int32_t n_graphs, uint64_t seed0) {
+  if (!b) return HGE_ERR_ARG;
+  BGUARD_BEGIN
+  static_assert(HGE_GOSSIP_MAX_OP_LAG < GLAG && 5ll * HGE_GOSSIP_MAX_EVENTS < (1 << 24), "kg_walk's ring and map entry");
+  if (hge_gossip_params_check(b->N, p, n_graphs) != HGE_OK)
+    throw Error{HGE_ERR_ARG, "hge_batch_generate: bad argument (hge_gossip_params_check)"};
+  b->generate(*p, n_graphs, seed0);
+  return HGE_OK;
+  BGUARD_END(b)
+}
+
+int hge_batch_clear(hge_batch* b) {
+  if (!b) return HGE_ERR_ARG;
+  BGUARD_BEGIN
+  if (b->st) HGE_HIPCHK(hipStreamSynchronize(b->st));
+  b->clear();
+  return HGE_OK;
+  BGUARD_END(b)
+}
+
+int64_t hge_batch_submissions(hge_batch* b, int32_t g, hge_event* ev_out, int32_t* status_out, int64_t cap) {
+  if (!b || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
+  BGUARD_BEGIN
+  return b->submissions(g, ev_out, status_out, cap);
+  BGUARD_END(b)
+}
+
 int hge_batch_kernel_ms(hge_batch* b, float* ms, int32_t cap) {
   if (!b || (!ms && cap > 0)) return HGE_ERR_ARG;
   for (int k = 0; k < hge_batch::NK && k < cap; k++) ms[k] = b->kms[k];
@@ -2221,7 +2442,7 @@ int hge_batch_kernel_ms(hge_batch* b, float* ms, int32_t cap) {
 // diagnostics (not part of the C ABI): graph g's lastAncestors (which 0) or
 // firstDescendants (which 1) rows after a run, E x N int32 into out
 extern "C" int hgb_debug_rows(hge_batch* b, int32_t g, int32_t which, int32_t* out) {
-  if (!b || !out || g < 0 || g >= (int)b->gs.size() || !b->ran) return HGE_ERR_ARG;
+  if (!b || !out || g < 0 || g >= b->graphs() || !b->ran) return HGE_ERR_ARG;
   BGUARD_BEGIN
   const GDesc& d = b->hd[g];
   if (which == 2)  // the run layout FDT[j][c][p], N x N x ccap

@@ -96,6 +96,8 @@ EXPORTS = [
     "hge_batch_create", "hge_batch_destroy", "hge_batch_last_error", "hge_batch_add", "hge_batch_stage",
     "hge_batch_run", "hge_batch_graphs", "hge_batch_info", "hge_batch_results", "hge_batch_kernel_ms",
     "hge_batch_fallbacks", "hge_batch_set_delivery", "hge_batch_delivery", "hge_batch_commits_view",
+    # ... generated on the device (hge_batch_gen.hip)
+    "hge_gossip_params_check", "hge_batch_generate", "hge_batch_clear", "hge_batch_submissions",
     # the wire / hashing format (host only, hge_gob.cpp)
     "hge_gob_encode_wire_events", "hge_gob_decode_wire_events", "hge_gob_encode_event_body",
 ]
@@ -108,6 +110,18 @@ class BatchCommits(ctypes.Structure):
     _fields_ = [("ids", ctypes.POINTER(ctypes.c_int32)), ("rr", ctypes.POINTER(ctypes.c_int32)),
                 ("cts", ctypes.POINTER(ctypes.c_int64)), ("counts", ctypes.POINTER(ctypes.c_int64)),
                 ("ordered", ctypes.c_int64), ("calls", ctypes.c_int64)]
+
+
+class GossipParams(ctypes.Structure):
+    """hge_gossip_params (hge.h)."""
+    _fields_ = [("events", ctypes.c_int64), ("forkers", ctypes.c_int32), ("fork_p", ctypes.c_double),
+                ("cascade_p", ctypes.c_double), ("op_lag", ctypes.c_int32), ("k", ctypes.c_int64)]
+
+
+def gossip_params_check(n_participants, graphs, events, k, forkers=0, fork_p=0.0, cascade_p=0.0, op_lag=0):
+    """hge_batch_generate's argument check (host only): 0 or HGE_ERR_ARG."""
+    p = GossipParams(events, forkers, fork_p, cascade_p, op_lag, k)
+    return int(lib().hge_gossip_params_check(n_participants, ctypes.byref(p), graphs))
 
 
 class _HostView:
@@ -283,6 +297,12 @@ def lib():
         L.hge_batch_delivery.argtypes = [vp]
         L.hge_batch_delivery.restype = i32
         L.hge_batch_commits_view.argtypes = [vp, i32, P(BatchCommits)]
+    if hasattr(L, "hge_batch_generate"):
+        L.hge_gossip_params_check.argtypes = [i32, vp, i32]  # (a GossipParams by reference)
+        L.hge_batch_generate.argtypes = [vp, vp, i32, ctypes.c_uint64]
+        L.hge_batch_clear.argtypes = [vp]
+        L.hge_batch_submissions.argtypes = [vp, i32, ctypes.c_void_p, P(i32), i64]
+        L.hge_batch_submissions.restype = i64
     _lib = L
     return L
 
@@ -1071,8 +1091,9 @@ class Engine:
 class Batch:
     """Many independent hashgraphs of N <= 64 participants replayed together on one
     GPU (hge_batch_*: one launch per stage for the whole batch).  add() admits a
-    graph's stream (hge_replay's conventions), run() replays every graph, state(g)
-    gives graph g's full state in tests/golden/digest.py's layout."""
+    graph's stream (hge_replay's conventions), or generate() has the device generate,
+    admit and stage counter_gossip streams from a seed; run() replays every graph,
+    state(g) gives graph g's full state in tests/golden/digest.py's layout."""
 
     def __init__(self, n_participants, device=0):
         self.L = lib()
@@ -1109,6 +1130,41 @@ class Batch:
                                          ctypes.byref(g)))
         self.status.append(st[:len(ev)])
         return g.value
+
+    def generate(self, events, k, graphs, seed, forkers=0, fork_p=0.0, cascade_p=0.0, op_lag=0):
+        """Append `graphs` graphs generated on the device (hge_batch_generate): graph i is
+        gossip.counter_gossip(n, events, seed + i, forkers, fork_p, cascade_p, op_lag) under
+        gossip.schedule(its submissions, k).  Nothing runs until stage() / run().  A batch
+        holds either added or generated graphs (HgeError otherwise, until clear()).
+        Returns the first new graph's index."""
+        p = GossipParams(events, forkers, fork_p, cascade_p, op_lag, k)
+        g0 = self.graphs()
+        self._check(self.L.hge_batch_generate(self.h, ctypes.byref(p), graphs, seed & 0xFFFFFFFFFFFFFFFF))
+        self.status.extend([None] * graphs)  # read back on demand (submissions)
+        return g0
+
+    def clear(self):
+        """Forget every graph and keep every allocation (hge_batch_clear): a sweep
+        generates, runs, reads what it wants, clears and generates the next seeds."""
+        self._check(self.L.hge_batch_clear(self.h))
+        self.status = []
+
+    def submissions(self, g):
+        """Generated graph g's raw submission stream and admission results, read back
+        from the device after stage(): counter_gossip's dict plus `status` (the event's id
+        in its graph or a negative hge status, as add()'s)."""
+        n = self.L.hge_batch_submissions(self.h, g, None, None, 0)
+        if n < 0:
+            self._check(int(n))
+        ev = np.zeros(max(n, 1), EVENT_DTYPE)
+        st = np.zeros(max(n, 1), np.int32)
+        m = self.L.hge_batch_submissions(self.h, g, ev.ctypes.data, _p32(st), n)
+        if m < 0:
+            self._check(int(m))
+        ev, st = ev[:n], st[:n]
+        return dict(n=self.n, creator=ev["creator"].copy(), index=ev["index"].copy(), sp=ev["self_parent"].copy(),
+                    op=ev["other_parent"].copy(), ts=ev["timestamp_ns"].copy(), S=ev["s"].copy(),
+                    hash=ev["hash"].copy(), ntx=ev["n_tx"].copy(), honest=ev["reserved"] == 0, status=st)
 
     def stage(self):
         self._check(self.L.hge_batch_stage(self.h))
@@ -1191,6 +1247,8 @@ class Batch:
                                              wit.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _p32(rr),
                                              _p64(cts), fame.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
                                              _p32(und)))
+        if self.status[g] is None:  # a generated graph: the device's admission results
+            self.status[g] = self.submissions(g)["status"]
         return dict(status=self.status[g], order=order[:inf["ordered"]], counts=counts[:K], rounds=rounds[:E],
                     witness=wit[:E].astype(bool), fame=fame[:R], rr=rr[:E], cts=cts[:E],
                     undetermined=und[:inf["undetermined"]],

@@ -25,6 +25,11 @@ hashgraph.go:373-376), and with probability 1/2 a third creator submits an
 event whose other-parent is the rejected one (rejected again).  Rejected
 submissions are never referenced by honest ones, so the honest stream goes on
 (the node keeps syncing with everyone else).
+
+random_gossip draws from numpy's generator in vectorised passes; counter_gossip is the
+same family as a sequential walk whose every decision is a word keyed by (seed, family,
+step), which the batch engine's device front restates (csrc/hge_batch_gen.hip,
+DESIGN.md §4.8).  The two give different streams for one seed.
 """
 import numpy as np
 
@@ -250,6 +255,145 @@ def _inject_cascades(dag, rng, p, seed):
     out["S"] = S
     out["hash"] = H
     return out
+
+
+# counter_gossip's key families (the `salt` of _bytes32)
+FAM_S, FAM_HASH, FAM_TWIN_S, FAM_TWIN_HASH, FAM_DOOMED_S, FAM_DOOMED_HASH = 1, 2, 3, 4, 5, 6
+FAM_STEP, FAM_CASCADE, FAM_FORKER = 7, 8, 9
+# a submission's kind: the honest event of a step, its fork twin, the cascade's records
+# 1 and 2, and record 3 at place 1 (no record 2) or place 2 after the twin
+KIND_HONEST, KIND_TWIN, KIND_REC1, KIND_REC2, KIND_REC3, KIND_REC3_LATE = 0, 1, 2, 3, 4, 5
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _word(seed, family, row, k):
+    """Word k of _bytes32(seed, family, .)[row] as a Python int."""
+    base = ((seed * 0x100000001B3 + family * 0x9E3779B1) & _M64) * 7919
+    z = x = (row * 4 + k + base + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    del x
+    return z ^ (z >> 31)
+
+
+def bernoulli_threshold(p):
+    """T = floor(p * 2^32): a decision is `u32 < T`, so p = 1 is always true."""
+    assert 0.0 <= p <= 1.0
+    return int(p * 4294967296.0)
+
+
+def counter_forkers(n, seed, forkers):
+    """counter_gossip's forker set: the min(forkers, n) creators of smallest (score, creator)."""
+    scores = sorted((_word(seed, FAM_FORKER, c, 0), c) for c in range(n))
+    return {c for _, c in scores[:min(forkers, n)]}
+
+
+def counter_gossip(n, events, seed, forkers=0, fork_p=0.0, cascade_p=0.0, op_lag=0):
+    """random_gossip's stream family (the module docstring and random_gossip's own) as a
+    sequential walk over the honest steps t = 0..events-1 whose every random decision is
+    a word of _bytes32(seed, family, row): a decision depends on (seed, t) alone, never
+    on generator state, so a device restates the walk word for word
+    (csrc/hge_batch_gen.hip).  Same keys as random_gossip, `honest` included.
+
+    hi32 / lo32 are the halves of a 64-bit word w_k, `u*m >> 32` maps a 32-bit u to
+    [0, m), and a Bernoulli(p) decision is u < floor(p * 2^32) (bernoulli_threshold).
+
+    Step t < n: the initial event of creator t (index 0, no parents).
+    Step t >= n, family FAM_STEP row t: creator a = hi32(w0)*n >> 32; peer
+    b = lo32(w0)*(n-1) >> 32, b += (b >= a) (n = 1: b = a); lag = hi32(w1)*(op_lag+1) >> 32;
+    the event is (a, len[a], head[a], the peer's event max(0, len[b]-1-lag) positions
+    into its chain), with len / head over the honest events so far.
+    Forkers, family FAM_FORKER row c: the min(forkers, n) creators of smallest
+    (w0, c).  A step t >= n of a forker forks iff lo32(w1) of its FAM_STEP row < T(fork_p):
+    the twin follows at once with the same creator, index and parents.
+    Cascade after a twin at n > 1, family FAM_CASCADE row t, iff hi32(w0) < T(cascade_p):
+      record 1: c2 = lo32(w0)*(n-1) >> 32, += (c2 >= a); (c2, len[c2], head[c2], the twin);
+      record 2 iff bit 63 of w1: o = lo32(w1)*(n-1) >> 32, += (o >= a);
+                (c2, len[c2]+1, record 1, head[o]);
+      record 3 iff bit 63 of w2 and n > 2: c3 = lo32(w2)*(n-2) >> 32, += (c3 >= min(a, c2)),
+                += (c3 >= max(a, c2)); (c3, len[c3], head[c3], record 1).
+    Fields: an honest event has ts = TS_BASE + 1000 t, S / hash = FAM_S / FAM_HASH row t;
+    a twin ts + 1 and FAM_TWIN_* row t; record r (1..3) ts + 2 + its place after the twin
+    and FAM_DOOMED_* row 4 t + r.  ntx = 1 everywhere."""
+    assert n >= 1 and events >= n and forkers >= 0 and op_lag >= 0
+    t_fork, t_casc = bernoulli_threshold(fork_p), bernoulli_threshold(cascade_p)
+    fset = counter_forkers(n, seed, forkers)
+    chains = [[] for _ in range(n)]  # honest submissions of every creator, in order
+    rows = []  # (creator, index, sp, op, t, kind)
+    # the words of every step at once (the loop below reads them as Python ints)
+    step_w = _bytes32(seed, FAM_STEP, events).view(">u8")[:, :2].tolist()
+    casc_w = _bytes32(seed, FAM_CASCADE, events).view(">u8")[:, :3].tolist() if t_fork and t_casc else None
+    for t in range(events):
+        if t < n:
+            chains[t].append(len(rows))
+            rows.append((t, 0, -1, -1, t, KIND_HONEST))
+            continue
+        w0, w1 = step_w[t]
+        a = ((w0 >> 32) * n) >> 32
+        b = a
+        if n > 1:
+            b = ((w0 & 0xFFFFFFFF) * (n - 1)) >> 32
+            b += b >= a
+        lag = ((w1 >> 32) * (op_lag + 1)) >> 32
+        ev = (a, len(chains[a]), chains[a][-1], chains[b][max(0, len(chains[b]) - 1 - lag)])
+        chains[a].append(len(rows))
+        rows.append(ev + (t, KIND_HONEST))
+        if a not in fset or not (w1 & 0xFFFFFFFF) < t_fork:
+            continue
+        twin = len(rows)
+        rows.append(ev + (t, KIND_TWIN))
+        if n < 2 or not t_casc:
+            continue
+        c0, c1, c2w = casc_w[t]
+        if not (c0 >> 32) < t_casc:
+            continue
+        c2 = ((c0 & 0xFFFFFFFF) * (n - 1)) >> 32
+        c2 += c2 >= a
+        rec1 = len(rows)
+        rows.append((c2, len(chains[c2]), chains[c2][-1], twin, t, KIND_REC1))
+        late = False
+        if c1 >> 63:
+            o = ((c1 & 0xFFFFFFFF) * (n - 1)) >> 32
+            o += o >= a
+            rows.append((c2, len(chains[c2]) + 1, rec1, chains[o][-1], t, KIND_REC2))
+            late = True
+        if c2w >> 63 and n > 2:
+            c3 = ((c2w & 0xFFFFFFFF) * (n - 2)) >> 32
+            c3 += c3 >= min(a, c2)
+            c3 += c3 >= max(a, c2)
+            rows.append((c3, len(chains[c3]), chains[c3][-1], rec1, t, KIND_REC3_LATE if late else KIND_REC3))
+    r = np.array(rows, np.int64).reshape(len(rows), 6)
+    return stream_fields(n, seed, r[:, 0], r[:, 1], r[:, 2], r[:, 3], r[:, 4] * 8 + r[:, 5])
+
+
+def stream_fields(n, seed, creator, index, sp, op, step):
+    """counter_gossip's dict from the structural fields and step = t * 8 + kind."""
+    step = np.asarray(step, np.int64)
+    t, kind = step >> 3, step & 7
+    E = len(step)
+    place = np.array([0, 1, 2, 3, 3, 4], np.int64)[kind]  # ts offset: twin 1, record at place k: 2 + k
+    S = np.empty((E, 32), np.uint8)
+    H = np.empty((E, 32), np.uint8)
+    tmax = int(t.max()) + 1 if E else 0
+    for sel, fs, fh, row, nrow in (
+            (kind == KIND_HONEST, FAM_S, FAM_HASH, t, tmax),
+            (kind == KIND_TWIN, FAM_TWIN_S, FAM_TWIN_HASH, t, tmax),
+            (kind >= KIND_REC1, FAM_DOOMED_S, FAM_DOOMED_HASH, 4 * t + np.minimum(kind - 1, 3), 4 * tmax)):
+        if sel.any():
+            S[sel] = _bytes32(seed, fs, nrow)[row[sel]]
+            H[sel] = _bytes32(seed, fh, nrow)[row[sel]]
+    return {
+        "n": n,
+        "creator": np.asarray(creator).astype(np.int32),
+        "index": np.asarray(index).astype(np.int32),
+        "sp": np.asarray(sp).astype(np.int32),
+        "op": np.asarray(op).astype(np.int32),
+        "ts": TS_BASE + 1000 * t + place,
+        "S": S,
+        "hash": H,
+        "ntx": np.ones(E, np.int32),
+        "honest": kind == KIND_HONEST,
+    }
 
 
 def schedule(n_submissions, k):

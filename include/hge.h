@@ -274,6 +274,48 @@ typedef struct {
  * counts from them as well. */
 int hge_batch_commits_view(hge_batch* b, int32_t g, hge_batch_commits* out);
 
+/* ---- a batch generated on the device (hge_batch_gen.hip) --------- */
+/* A Monte Carlo sweep's events come from a seeded generator, not from a peer: the
+ * batch's graphs are generated, admitted (hge_batch_add's rules, in its order, on every
+ * submission) and laid out in the staged tables by kernels, and every later stage runs
+ * as on added graphs.  The stream family is babble_amd/gossip.py's counter_gossip:
+ * random gossip, fork twins and cascades whose every random decision is a SplitMix64
+ * word keyed by (seed, family, step), reproducible on the host field for field. */
+typedef struct hge_gossip_params {
+  int64_t events;   /* honest events per graph, N .. HGE_GOSSIP_MAX_EVENTS            */
+  int32_t forkers;  /* creators that fork (the min(forkers, N) of smallest score)      */
+  double fork_p;    /* a forker's event gets a twin with this probability, [0, 1]      */
+  double cascade_p; /* a twin is built upon with this probability, [0, 1]              */
+  int32_t op_lag;   /* other-parents up to op_lag behind their chain's head,
+                       0 .. HGE_GOSSIP_MAX_OP_LAG                                      */
+  int64_t k;        /* RunConsensus after every k submissions and after the last one   */
+} hge_gossip_params;
+#define HGE_GOSSIP_MAX_OP_LAG 31        /* the walk keeps each chain's last 32 positions           */
+#define HGE_GOSSIP_MAX_EVENTS 3000000   /* 5 submissions a step at most, ids below 2^24            */
+/* hge_batch_generate's argument check, host only: HGE_ERR_ARG for n_participants outside
+ * [1, 64], n_graphs < 1, events < n_participants or above the cap, a probability outside
+ * [0, 1], forkers < 0, k < 1, op_lag outside its cap. */
+int hge_gossip_params_check(int32_t n_participants, const hge_gossip_params* p, int32_t n_graphs);
+/* Append n_graphs graphs: graph i is counter_gossip(N, events, seed0 + i, forkers, fork_p,
+ * cascade_p, op_lag) with RunConsensus after every k submissions and after the last one
+ * (the call points stored as accepted counts, as hge_batch_add stores them).  Nothing runs
+ * until hge_batch_stage / hge_batch_run; bad arguments (hge_gossip_params_check) return
+ * HGE_ERR_ARG before the device is touched.  A batch holds either added or generated
+ * graphs: hge_batch_generate after hge_batch_add, or the reverse, is HGE_ERR_ARG until
+ * hge_batch_clear.  Generated graphs keep no host mirror: info, results, delivery and
+ * the fallback path serve them from device state. */
+int hge_batch_generate(hge_batch* b, const hge_gossip_params* p, int32_t n_graphs, uint64_t seed0);
+/* Forget every graph, added or generated, and keep every allocation: generate, run, read
+ * the scalars, clear, generate the next seeds. */
+int hge_batch_clear(hge_batch* b);
+/* Graph g's raw submission stream and each submission's admission result (the event's id
+ * in its graph or a negative hge_status, as hge_batch_add's status_out), read back from
+ * the device after hge_batch_stage; ev_out[i].reserved is submission i's kind (0 honest, 1
+ * fork twin, 2.. cascade records).  Returns the number of submissions, or a negative
+ * hge_status; nothing is written when cap is smaller (either pointer may be NULL).  For
+ * tests and for exporting a graph of interest: not on the run path.  Generated batches only. */
+int64_t hge_batch_submissions(hge_batch* b, int32_t g, hge_event* ev_out, int32_t* status_out, int64_t cap);
+
 /* ---- one hashgraph split across GPUs (babble_amd/dist.py) ------ */
 /* Sharded replay.  Every rank stages the whole stream (hge_replay_prepare) and
  * makes the same plan: part p owns the events [ev_bounds[p], ev_bounds[p+1]) and
