@@ -139,6 +139,9 @@ struct BT {
   // that every other field keeps its offset in the kernels' arguments.
   int32_t* ord_rr;       // [eo + k] round received of order[eo + k]
   int64_t* ord_cts;      // [eo + k] its consensus timestamp
+  // kb_consensus: the call whose batch committed x (the bulk path's is rcall), read by the
+  // statistics pass (hge_batch_stats.hip).  After ord_cts for the same reason.
+  int32_t* xcc;          // [eo + x]
 };
 
 __device__ __forceinline__ int rl(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
@@ -1352,6 +1355,7 @@ __global__ __launch_bounds__(256, OCC) void kb_consensus(BT t) {
           }
           t.rr[eo + x] = found;
           t.cts[eo + x] = med;
+          t.xcc[eo + x] = c;
           const int p = nb + preR[k] + __popcll(rec & below);
           if (p < KB && lds_keys) {
             kri[p] = (uint32_t)found << 16 | (uint32_t)x;
@@ -1456,6 +1460,7 @@ __global__ __launch_bounds__(256, OCC) void kb_consensus(BT t) {
 
 #include "hge_batch_bulk.hip"
 #include "hge_batch_gen.hip"
+#include "hge_batch_stats.hip"
 
 }  // namespace hgb
 
@@ -1579,6 +1584,14 @@ struct hge_batch {
   DBuf<GenG> d_gg;
   DBuf<int32_t> d_gmap, d_gcnt, d_scr, d_six, d_ssp, d_sop, d_sstep, d_sst, d_sacc, d_estep;
   DBuf<hge_event> d_raw;
+  // the statistics pass (hge_batch_stats, hge_batch_stats.hip): valid from a run until the
+  // batch changes; which graphs kb_consensus replayed (the source of an event's commit
+  // call), its table, and the pass's grow-only scratch and results
+  bool stats_ok = false;
+  std::vector<int32_t> h_path;
+  DBuf<int32_t> d_xcc, d_path;
+  DBuf<int64_t> d_spart, d_sout;
+  std::vector<int64_t> h_sout;
 
   int graphs() const { return gen.empty() ? (int)gs.size() : (int)gen.size(); }
 
@@ -1667,6 +1680,7 @@ struct hge_batch {
     }
     staged = false;
     ran = false;
+    stats_ok = false;
     return (int)gs.size() - 1;
   }
 
@@ -1677,6 +1691,7 @@ struct hge_batch {
   }
 
   void stage() {
+    stats_ok = false;
     if (staged) {
       ensure_delivery();
       return;
@@ -1780,6 +1795,7 @@ struct hge_batch {
     }
     staged = false;
     ran = false;
+    stats_ok = false;
   }
 
   void clear() {
@@ -1788,6 +1804,7 @@ struct hge_batch {
     hd.clear();
     staged = false;
     ran = false;
+    stats_ok = false;
     delivered = 0;
     n_fallback = 0;
   }
@@ -1990,6 +2007,7 @@ struct hge_batch {
     d_wlc.need(1);
     d_gctx.need(G);
     d_cinf.need(E1);
+    d_xcc.need(E1);
   }
 
   BT tables() const {
@@ -2071,6 +2089,7 @@ struct hge_batch {
     t.wlc = d_wlc.p;
     t.gctx = d_gctx.p;
     t.cinf = d_cinf.p;
+    t.xcc = d_xcc.p;
     return t;
   }
 
@@ -2145,7 +2164,11 @@ struct hge_batch {
     stage();
     delivered = 0;
     const int G = graphs();
-    if (G == 0) return 0;
+    if (G == 0) {
+      h_path.clear();
+      stats_ok = true;
+      return 0;
+    }
     const size_t RN = (size_t)std::max<int64_t>(Rtot, 1) * N;
     const size_t E1 = (size_t)std::max<int64_t>(Etot, 1);
     const size_t K1 = (size_t)std::max<int64_t>(Ktot, 1);
@@ -2193,6 +2216,8 @@ struct hge_batch {
     for (int g = 0; g < G; g++)
       if (serial || (h_scal[(size_t)g * 8 + 7] && !h_scal[(size_t)g * 8 + 6])) fb.push_back(g);
     n_fallback = (int64_t)fb.size();
+    h_path.assign((size_t)G, 0);
+    for (int32_t g : fb) h_path[(size_t)g] = 1;
     if (!fb.empty()) {
       HGE_HIPCHK(hipMemcpyAsync(d_glist.p, fb.data(), fb.size() * 4, hipMemcpyHostToDevice, st));
       t.glist = d_glist.p;
@@ -2241,7 +2266,64 @@ struct hge_batch {
     delivered = mode;
     delivered_what = deliver;
     ran = true;
+    stats_ok = true;
     return tot;
+  }
+
+  // The last run's statistics: three launches over the state in HBM, one copy, one wait.
+  // A graph is cut into nb spans while the batch alone would leave compute units idle.
+  void stats(const hge_stats_spec& s, int64_t* rows, int64_t* hist, int64_t* ghist) {
+    const int G = graphs();
+    const int64_t HL = hge_stats::hist_len(s);
+    if (G == 0) {
+      memset(hist, 0, (size_t)HL * 8);
+      return;
+    }
+    HGE_HIPCHK(hipSetDevice(device));
+    const int64_t per = (4 * (int64_t)ncu + G - 1) / G, cut = ((int64_t)Emax + 4095) / 4096;
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(per, cut), 1024));
+    const int64_t C = KS_ROW + HL;
+    d_spart.need((size_t)G * nb * C);
+    d_sout.need((size_t)(HL + (int64_t)G * C));
+    d_path.need((size_t)G);
+    HGE_HIPCHK(hipMemcpyAsync(d_path.p, h_path.data(), (size_t)G * 4, hipMemcpyHostToDevice, st));
+    ST t{};
+    t.s = s;
+    t.N = N;
+    t.ccap = ccap;
+    t.G = G;
+    t.nb = nb;
+    t.span = std::max<int64_t>(1, ((int64_t)Emax + nb - 1) / nb);
+    t.gd = d_gd.p;
+    t.round = d_round.p;
+    t.rr = d_rr.p;
+    t.cr = d_cr.p;
+    t.ix = d_ix.p;
+    t.rcall = d_rcall.p;
+    t.xcc = d_xcc.p;
+    t.W = d_W.p;
+    t.path = d_path.p;
+    t.cts = d_cts.p;
+    t.ts = d_ts.p;
+    t.calls = d_calls.p;
+    t.scal = d_scal.p;
+    t.fame = d_fame.p;
+    t.part = d_spart.p;
+    t.out = d_sout.p;
+    hipLaunchKernelGGL(ks_events, dim3((unsigned)nb, (unsigned)G), dim3(KS_NT), 0, st, t);
+    HGE_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ks_finish, dim3((unsigned)G), dim3(KS_NT), 0, st, t);
+    HGE_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ks_total, dim3((unsigned)((HL + 63) / 64)), dim3(1024), 0, st, t);
+    HGE_HIPCHK(hipGetLastError());
+    // totals | rows | slabs: the prefix the caller asked for
+    const size_t n = (size_t)(HL + (rows || ghist ? (int64_t)G * KS_ROW : 0) + (ghist ? (int64_t)G * HL : 0));
+    h_sout.resize(n);
+    HGE_HIPCHK(hipMemcpyAsync(h_sout.data(), d_sout.p, n * 8, hipMemcpyDeviceToHost, st));
+    HGE_HIPCHK(hipStreamSynchronize(st));
+    memcpy(hist, h_sout.data(), (size_t)HL * 8);
+    if (rows) memcpy(rows, h_sout.data() + HL, (size_t)G * KS_ROW * 8);
+    if (ghist) memcpy(ghist, h_sout.data() + HL + (size_t)G * KS_ROW, (size_t)G * HL * 8);
   }
 
   template <typename T>
@@ -2411,6 +2493,24 @@ int hge_batch_generate(hge_batch* b, const hge_gossip_params* p, int32_t n_graph
   if (hge_gossip_params_check(b->N, p, n_graphs) != HGE_OK)
     throw Error{HGE_ERR_ARG, "hge_batch_generate: bad argument (hge_gossip_params_check)"};
   b->generate(*p, n_graphs, seed0);
+  return HGE_OK;
+  BGUARD_END(b)
+}
+
+int hge_stats_spec_check(const hge_stats_spec* s) { return hge_stats::spec_ok(s) ? HGE_OK : HGE_ERR_ARG; }
+
+int64_t hge_stats_hist_len(const hge_stats_spec* s) {
+  return hge_stats::spec_ok(s) ? hge_stats::hist_len(*s) : (int64_t)HGE_ERR_ARG;
+}
+
+int hge_batch_stats(hge_batch* b, const hge_stats_spec* s, int64_t* graph_rows, int64_t* hist, int64_t* graph_hist) {
+  if (!b) return HGE_ERR_ARG;
+  BGUARD_BEGIN
+  if (!hge_stats::spec_ok(s)) throw Error{HGE_ERR_ARG, "hge_batch_stats: bad spec (hge_stats_spec_check)"};
+  if (!hist) throw Error{HGE_ERR_ARG, "hge_batch_stats: hist is NULL"};
+  if (!b->stats_ok)
+    throw Error{HGE_ERR_ARG, "hge_batch_stats: no run since the batch last changed (hge_batch_run)"};
+  b->stats(*s, graph_rows, hist, graph_hist);
   return HGE_OK;
   BGUARD_END(b)
 }

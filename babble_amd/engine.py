@@ -98,6 +98,8 @@ EXPORTS = [
     "hge_batch_fallbacks", "hge_batch_set_delivery", "hge_batch_delivery", "hge_batch_commits_view",
     # ... generated on the device (hge_batch_gen.hip)
     "hge_gossip_params_check", "hge_batch_generate", "hge_batch_clear", "hge_batch_submissions",
+    # ... and a run's statistics reduced on the device (hge_batch_stats.hip)
+    "hge_stats_spec_check", "hge_stats_hist_len", "hge_batch_stats",
     # the wire / hashing format (host only, hge_gob.cpp)
     "hge_gob_encode_wire_events", "hge_gob_decode_wire_events", "hge_gob_encode_event_body",
 ]
@@ -116,6 +118,42 @@ class GossipParams(ctypes.Structure):
     """hge_gossip_params (hge.h)."""
     _fields_ = [("events", ctypes.c_int64), ("forkers", ctypes.c_int32), ("fork_p", ctypes.c_double),
                 ("cascade_p", ctypes.c_double), ("op_lag", ctypes.c_int32), ("k", ctypes.c_int64)]
+
+
+INT64_MAX = (1 << 63) - 1
+STATS_MAX_BINS = 256
+# the per-graph row of Batch.stats() (hge_stats_field in hge.h)
+STATS_FIELDS = ("events", "in_range", "ordered", "censored", "rounds", "lcr", "witnesses", "famous", "not_famous",
+                "undecided", "dround_sum", "dround_max", "dcall_sum", "dcall_max", "lag_sum", "lag_max", "dts_sum",
+                "dts_min", "dts_max", "path", "reserved20", "reserved21", "reserved22", "reserved23")
+STATS_ROW_DTYPE = np.dtype([(f, "<i8") for f in STATS_FIELDS])
+
+
+class StatsSpec(ctypes.Structure):
+    """hge_stats_spec (hge.h; the bin rules: csrc/hge_stats.h).  The defaults: 16 round
+    bins, 64 call bins, 64 lag bins of 32 events (Batch.stats() without a spec: of N events, N the
+    batch's participants), 64 timestamp bins of 10 us from 0 (one
+    below and one above them), every event."""
+    _fields_ = [("round_bins", ctypes.c_int32), ("call_bins", ctypes.c_int32), ("lag_bins", ctypes.c_int32),
+                ("ts_bins", ctypes.c_int32), ("lag_bin", ctypes.c_int64), ("ts_bin", ctypes.c_int64),
+                ("ts_lo", ctypes.c_int64), ("x_lo", ctypes.c_int64), ("x_hi", ctypes.c_int64)]
+
+    def __init__(self, round_bins=16, call_bins=64, lag_bins=64, ts_bins=64, lag_bin=32, ts_bin=10_000, ts_lo=0,
+                 x_lo=0, x_hi=INT64_MAX):
+        super().__init__(round_bins, call_bins, lag_bins, ts_bins, lag_bin, ts_bin, ts_lo, x_lo, x_hi)
+
+    def check(self):
+        """hge_stats_spec_check (host only): 0 or HGE_ERR_ARG."""
+        return int(lib().hge_stats_spec_check(ctypes.byref(self)))
+
+    def hist_len(self):
+        """round_bins + call_bins + lag_bins + ts_bins + 2, or HGE_ERR_ARG for a bad spec."""
+        return int(lib().hge_stats_hist_len(ctypes.byref(self)))
+
+    def split(self, hist):
+        """The histogram array (last axis hist_len) as dict(round=, call=, lag=, ts=) of views."""
+        a, b, c = self.round_bins, self.round_bins + self.call_bins, self.round_bins + self.call_bins + self.lag_bins
+        return dict(round=hist[..., :a], call=hist[..., a:b], lag=hist[..., b:c], ts=hist[..., c:])
 
 
 def gossip_params_check(n_participants, graphs, events, k, forkers=0, fork_p=0.0, cascade_p=0.0, op_lag=0):
@@ -303,6 +341,11 @@ def lib():
         L.hge_batch_clear.argtypes = [vp]
         L.hge_batch_submissions.argtypes = [vp, i32, ctypes.c_void_p, P(i32), i64]
         L.hge_batch_submissions.restype = i64
+    if hasattr(L, "hge_batch_stats"):
+        L.hge_stats_spec_check.argtypes = [vp]  # (a StatsSpec by reference)
+        L.hge_stats_hist_len.argtypes = [vp]
+        L.hge_stats_hist_len.restype = i64
+        L.hge_batch_stats.argtypes = [vp, vp, P(i64), P(i64), P(i64)]
     _lib = L
     return L
 
@@ -1093,7 +1136,8 @@ class Batch:
     GPU (hge_batch_*: one launch per stage for the whole batch).  add() admits a
     graph's stream (hge_replay's conventions), or generate() has the device generate,
     admit and stage counter_gossip streams from a seed; run() replays every graph,
-    state(g) gives graph g's full state in tests/golden/digest.py's layout."""
+    state(g) gives graph g's full state in tests/golden/digest.py's layout, stats() the
+    run's consensus-latency statistics reduced on the device."""
 
     def __init__(self, n_participants, device=0):
         self.L = lib()
@@ -1215,6 +1259,29 @@ class Batch:
         self._check(self.L.hge_batch_info(self.h, g, _p64(a)))
         keys = ("events", "calls", "rounds", "lcr", "lcre", "transactions", "ordered", "undetermined")
         return dict(zip(keys, a.tolist()))
+
+    def stats(self, spec=None, per_graph_hist=False):
+        """The last run's consensus-latency statistics, reduced on the device
+        (hge_batch_stats; definitions in csrc/hge_stats.h): dict(graphs=a structured int64
+        array of one STATS_FIELDS row per graph, round=, call=, lag=, ts= the histograms
+        summed over the graphs, hist= the same four in one array, per_graph= None or
+        dict(round=, call=, lag=, ts=) of [graphs][bins] arrays).  One host wait; HgeError
+        (HGE_ERR_ARG) for a bad spec, before run(), and after add / generate / clear /
+        stage since the last run."""
+        spec = StatsSpec(lag_bin=self.n) if spec is None else spec
+        n = spec.hist_len()
+        if n < 0:
+            raise HgeError(n, "Batch.stats: bad spec (hge_stats_spec_check)")
+        G = max(self.graphs(), 0)
+        rows = np.zeros((max(G, 1), len(STATS_FIELDS)), np.int64)
+        hist = np.zeros(n, np.int64)
+        gh = np.zeros((max(G, 1), n), np.int64) if per_graph_hist else None
+        self._check(self.L.hge_batch_stats(self.h, ctypes.byref(spec), _p64(rows), _p64(hist),
+                                           _p64(gh) if per_graph_hist else None))
+        out = dict(graphs=rows[:G].view(STATS_ROW_DTYPE)[:, 0], hist=hist,
+                   per_graph=spec.split(gh[:G]) if per_graph_hist else None)
+        out.update(spec.split(hist))
+        return out
 
     KERNELS = ("kb_coords", "kb_fd", "kb_fdrows", "kb_front", "kb_fame", "kb_fold", "kb_receive", "kb_order")
 

@@ -316,6 +316,63 @@ int hge_batch_clear(hge_batch* b);
  * tests and for exporting a graph of interest: not on the run path.  Generated batches only. */
 int64_t hge_batch_submissions(hge_batch* b, int32_t g, hge_event* ev_out, int32_t* status_out, int64_t cap);
 
+/* ---- a run's consensus-latency statistics, reduced on the device (hge_batch_stats.hip,
+ * DESIGN.md §4.8) ----------------------------------------------------------------- */
+/* What a sweep asks of a run, without copying any per-event state to the host.  For an
+ * accepted event x that the last run ordered (definitions and bin rules:
+ * babble_amd/csrc/hge_stats.h):
+ *   dround = round received - round;  dcall = the call that committed x - the call that
+ *   inserted x;  lag = the events accepted after x when it was committed;
+ *   dts = consensus timestamp - the event's own timestamp.
+ * Only events with x_lo <= x < x_hi are counted (x: the event's id in its graph), so a
+ * caller can cut warm-up and the censored tail. */
+#define HGE_STATS_MAX_BINS 256
+#define HGE_STATS_GRAPH_FIELDS 24
+typedef struct hge_stats_spec {
+  int32_t round_bins, call_bins, lag_bins, ts_bins; /* each 1 .. HGE_STATS_MAX_BINS */
+  int64_t lag_bin, ts_bin;                          /* bin widths, >= 1 (ts: ts_bins bins from ts_lo, one
+                                                       below and one above them) */
+  int64_t ts_lo;
+  int64_t x_lo, x_hi;                               /* 0 <= x_lo <= x_hi; INT64_MAX = no upper bound */
+} hge_stats_spec;
+/* the per-graph row: int64 fields */
+enum hge_stats_field {
+  HGE_STATS_EVENTS = 0,        /* accepted events */
+  HGE_STATS_IN_RANGE = 1,      /* events in [x_lo, x_hi) */
+  HGE_STATS_ORDERED = 2,       /* those of them ordered */
+  HGE_STATS_CENSORED = 3,      /* those not ordered */
+  HGE_STATS_ROUNDS = 4,        /* Rounds() */
+  HGE_STATS_LCR = 5,           /* LastConsensusRound (-1 nil) */
+  HGE_STATS_WITNESSES = 6,     /* witnesses in rounds [0, Rounds()): unfiltered by the x range */
+  HGE_STATS_FAMOUS = 7,        /* of those: famous, */
+  HGE_STATS_NOT_FAMOUS = 8,    /* not famous, */
+  HGE_STATS_UNDECIDED = 9,     /* undecided */
+  HGE_STATS_DROUND_SUM = 10,
+  HGE_STATS_DROUND_MAX = 11,
+  HGE_STATS_DCALL_SUM = 12,
+  HGE_STATS_DCALL_MAX = 13,
+  HGE_STATS_LAG_SUM = 14,
+  HGE_STATS_LAG_MAX = 15,
+  HGE_STATS_DTS_SUM = 16,      /* wrapping mod 2^64 */
+  HGE_STATS_DTS_MIN = 17,
+  HGE_STATS_DTS_MAX = 18,
+  HGE_STATS_PATH = 19          /* 0 ordered in bulk, 1 replayed call by call (kb_consensus) */
+                               /* 20 .. 23: zero.  With nothing ordered in range, 10 .. 18 are 0. */
+};
+/* host only: HGE_ERR_ARG for a NULL spec, a bin count outside [1, HGE_STATS_MAX_BINS], a bin
+ * width below 1, x_lo < 0 or x_lo > x_hi; else HGE_OK */
+int hge_stats_spec_check(const hge_stats_spec* s);
+/* round_bins + call_bins + lag_bins + ts_bins + 2, or HGE_ERR_ARG for a bad spec */
+int64_t hge_stats_hist_len(const hge_stats_spec* s);
+/* The statistics of the last run, on demand: one reduction pass over the run's state in
+ * HBM and one host wait; the run itself is unchanged and the call may be repeated (with
+ * the same or another spec) with the same result.  hist[hist_len] holds the histograms
+ * round | call | lag | ts summed over all graphs; graph_rows[graphs][HGE_STATS_GRAPH_FIELDS]
+ * and graph_hist[graphs][hist_len] the same per graph (either may be NULL).  HGE_ERR_ARG:
+ * a bad spec (before the device is touched), a NULL hist, no run yet, or add / generate /
+ * clear / stage since the last run.  No graphs: HGE_OK and zeros. */
+int hge_batch_stats(hge_batch* b, const hge_stats_spec* s, int64_t* graph_rows, int64_t* hist, int64_t* graph_hist);
+
 /* ---- one hashgraph split across GPUs (babble_amd/dist.py) ------ */
 /* Sharded replay.  Every rank stages the whole stream (hge_replay_prepare) and
  * makes the same plan: part p owns the events [ev_bounds[p], ev_bounds[p+1]) and
