@@ -1565,6 +1565,11 @@ struct hge_batch {
   DBuf<int64_t> d_gctx, d_ctsch;
   int Emax = 0;
   int64_t n_fallback = 0;  // graphs the last run replayed through kb_consensus
+  // the kernel instances the last run chose from the batch's size (hge_batch_launch_plan):
+  // set where run_stages and run take their branches, 0 for a stage that did not launch
+  struct Plan {
+    int32_t nm = 0, coords = 0, front_threads = 0, ns = 0, sort_threads = 0, consensus_occ = 0, dlv = 0;
+  } plan;
   // the commit stream in host memory (hge_batch_set_delivery), pooled like the device
   // tables: ids / rr / cts at GDesc::eo, counts at GDesc::co
   uint32_t deliver = 0;   // requested: bit 0 order and counts, bit 1 rr and cts as well
@@ -1807,6 +1812,7 @@ struct hge_batch {
     stats_ok = false;
     delivered = 0;
     n_fallback = 0;
+    plan = Plan{};
   }
 
   GenT gen_tables() const {
@@ -2102,6 +2108,8 @@ struct hge_batch {
 
   template <int NM, bool DLV>
   void run_stages(int G, const BT& t) {
+    plan.nm = NM;
+    plan.dlv = DLV;
     // a workgroup of 1,024 threads per graph while two fit a CU, else 512
     // 1,024 threads per graph and the kb_levels pass while two graphs fit a CU, else
     // 512 threads levelling their own chunks
@@ -2113,10 +2121,12 @@ struct hge_batch {
       // the columns split over two workgroups while both still get a CU of their own
       // (128 graphs: 0.46 -> 0.43 ms; at 256 graphs, two per CU, 0.49 -> 0.51; four
       // 8-column parts: 0.45 / 0.55)
+      plan.coords = 2 * G <= ncu ? 0 : 1;
       if (2 * G <= ncu) hipLaunchKernelGGL((kb_coords<NM, 512, true, 2>), dim3(G * 2), dim3(512), 0, st, t);
       else launch(kb_coords<NM, 1024, true>, G, t, 1024);
       HGE_HIPCHK(hipGetLastError());
     } else {
+      plan.coords = 2;
       launch(kb_coords<NM, 512, false>, G, t, 512);
     }
     HGE_HIPCHK(hipEventRecord(ev[1], st));
@@ -2124,6 +2134,7 @@ struct hge_batch {
     HGE_HIPCHK(hipEventRecord(ev[2], st));
     launch(kb_fdrows<NM>, G * N, t, 256);  // rows for kb_front (kb_median reads the run layout)
     HGE_HIPCHK(hipEventRecord(ev[3], st));
+    plan.front_threads = G > 2 * ncu ? 256 : G > ncu ? 512 : 1024;
     if (G > 2 * ncu) launch(kb_front<NM, 256>, G, t, 256);
     else if (G > ncu) launch(kb_front<NM, 512>, G, t, 512);
     else launch(kb_front<NM, 1024>, G, t, 1024);
@@ -2133,6 +2144,7 @@ struct hge_batch {
       return;
     }
     launch(kb_prep<NM>, G, t, 1024);
+    plan.ns = G > 2 * ncu ? 2 : 3;
     if (G > 2 * ncu) hipLaunchKernelGGL((kb_pairs<NM, 2>), dim3(8, (unsigned)G), dim3(256), 0, st, t);
     else hipLaunchKernelGGL((kb_pairs<NM, 3>), dim3(8, (unsigned)G), dim3(256), 0, st, t);
     HGE_HIPCHK(hipGetLastError());
@@ -2152,6 +2164,7 @@ struct hge_batch {
     // call buckets: up to 1,024 keys one wave each (a workgroup of four while the
     // batch has few buckets), larger ones a workgroup each
     const int nbk = (int)std::min<int64_t>(std::max<int64_t>(Ktot, 1), (int64_t)ncu * 16);
+    plan.sort_threads = Ktot > 16 * (int64_t)ncu ? 64 : 256;
     if (Ktot > 16 * (int64_t)ncu) hipLaunchKernelGGL((kb_sort<64, 0, 1024, DLV>), dim3(nbk), dim3(64), 0, st, t, 0);
     else hipLaunchKernelGGL((kb_sort<256, 0, 1024, DLV>), dim3(nbk), dim3(256), 0, st, t, 0);
     HGE_HIPCHK(hipGetLastError());
@@ -2163,6 +2176,7 @@ struct hge_batch {
   int64_t run() {
     stage();
     delivered = 0;
+    plan = Plan{};
     const int G = graphs();
     if (G == 0) {
       h_path.clear();
@@ -2222,6 +2236,7 @@ struct hge_batch {
       HGE_HIPCHK(hipMemcpyAsync(d_glist.p, fb.data(), fb.size() * 4, hipMemcpyHostToDevice, st));
       t.glist = d_glist.p;
       const int F = (int)fb.size();
+      plan.consensus_occ = F > 2 * ncu ? 4 : 1;
       float ms = 0;
       HGE_HIPCHK(hipEventRecord(ev[7], st));
       auto replay = [&](auto kern_off, auto kern_on) {
@@ -2529,6 +2544,15 @@ int64_t hge_batch_submissions(hge_batch* b, int32_t g, hge_event* ev_out, int32_
   BGUARD_BEGIN
   return b->submissions(g, ev_out, status_out, cap);
   BGUARD_END(b)
+}
+
+int hge_batch_launch_plan(hge_batch* b, int32_t* out, int32_t cap) {
+  if (!b || (!out && cap > 0)) return HGE_ERR_ARG;
+  const hge_batch::Plan& p = b->plan;
+  const int32_t f[] = {b->ncu, p.nm, p.coords, p.front_threads, p.ns, p.sort_threads, p.consensus_occ, p.dlv};
+  const int n = (int)(sizeof(f) / sizeof(f[0]));
+  for (int k = 0; k < n && k < cap; k++) out[k] = f[k];
+  return n;
 }
 
 int hge_batch_kernel_ms(hge_batch* b, float* ms, int32_t cap) {

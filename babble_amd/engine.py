@@ -96,6 +96,7 @@ EXPORTS = [
     "hge_batch_create", "hge_batch_destroy", "hge_batch_last_error", "hge_batch_add", "hge_batch_stage",
     "hge_batch_run", "hge_batch_graphs", "hge_batch_info", "hge_batch_results", "hge_batch_kernel_ms",
     "hge_batch_fallbacks", "hge_batch_set_delivery", "hge_batch_delivery", "hge_batch_commits_view",
+    "hge_batch_launch_plan",
     # ... generated on the device (hge_batch_gen.hip)
     "hge_gossip_params_check", "hge_batch_generate", "hge_batch_clear", "hge_batch_submissions",
     # ... and a run's statistics reduced on the device (hge_batch_stats.hip)
@@ -346,6 +347,8 @@ def lib():
         L.hge_stats_hist_len.argtypes = [vp]
         L.hge_stats_hist_len.restype = i64
         L.hge_batch_stats.argtypes = [vp, vp, P(i64), P(i64), P(i64)]
+    if hasattr(L, "hge_batch_launch_plan"):
+        L.hge_batch_launch_plan.argtypes = [vp, P(i32), i32]
     _lib = L
     return L
 
@@ -1288,6 +1291,22 @@ class Batch:
     def fallbacks(self):
         """Graphs the last run replayed call by call (kb_consensus) instead of in bulk."""
         return int(self.L.hge_batch_fallbacks(self.h))
+
+    PLAN = ("cus", "nm", "coords", "front_threads", "ns", "sort_threads", "consensus_occ", "dlv")
+
+    def launch_plan(self):
+        """The kernel instances the last run chose from the batch's size
+        (hge_batch_launch_plan): dict(cus= the device's compute units, nm= 32 or 64,
+        coords= 0 levelled by two workgroups of 512 / 1 levelled by 1,024 threads / 2
+        self-levelling with 512, front_threads=, ns= kb_pairs' and kb_fold's pair slots,
+        sort_threads= per bucket of kb_sort's first class, consensus_occ= 0 when
+        kb_consensus was not launched, else 1 or 4, dlv=).  Everything but cus is 0 before
+        the first run; host values, no device work."""
+        a = (ctypes.c_int32 * len(self.PLAN))()
+        n = self.L.hge_batch_launch_plan(self.h, a, len(self.PLAN))
+        if n < 0:
+            self._check(n)
+        return dict(zip(self.PLAN, [int(a[k]) for k in range(n)]))
 
     def kernel_ms(self):
         """Device ms of the last run's stages (HIP events between the launches)."""

@@ -245,6 +245,20 @@ int hge_batch_kernel_ms(hge_batch* b, float* ms, int32_t cap);
 /* graphs the last run replayed call by call (kb_consensus) because the bulk fold
  * could not hold them (more than 256 rounds, or a receive-interval table overflow) */
 int64_t hge_batch_fallbacks(hge_batch* b);
+/* The kernel instances the last run chose from the batch's size (graphs G, calls in all,
+ * fallback graphs F, each against the device's compute-unit count), so a
+ * test can name what it ran.  out[8] = {cus: compute units of the device;
+ * nm: the width template, 32 or 64;
+ * coords: 0 levelled with two workgroups of 512 per graph, 1 levelled with 1,024 threads,
+ *         2 self-levelling with 512;
+ * front_threads: kb_front's workgroup, 1024 / 512 / 256;
+ * ns: DecideFame pair slots of kb_pairs and kb_fold, 3 or 2 (0 under HGB_SERIAL=1);
+ * sort_threads: threads per bucket of kb_sort's first size class, 256 or 64 (0 under HGB_SERIAL=1);
+ * consensus_occ: 0 when kb_consensus was not launched, else its occupancy build, 1 or 4;
+ * dlv: 1 when the instances that store rr / cts in commit order ran}.
+ * Before the first run (and after hge_batch_clear) everything but cus is 0.  Host values
+ * only: reading them, like setting them, adds no device work to a run.  Returns the field count. */
+int hge_batch_launch_plan(hge_batch* b, int32_t* out, int32_t cap);
 /* Delivery of the commit stream (what FindOrder hands its caller, hashgraph.go:723-760)
  * to host memory inside the run.  Off by default: a run then takes exactly the path it
  * takes without this mode and the orders stay on the device (hge_batch_results copies

@@ -126,6 +126,9 @@ def test_batch_many_graphs_one_launch_per_stage():
         assert set(ms) == {"kb_coords", "kb_fd", "kb_fdrows", "kb_front", "kb_fame", "kb_fold", "kb_receive",
                            "kb_order"}
         assert b.fallbacks() == 0  # every graph in bulk
+        # 256 graphs: one per compute unit of an MI355X (test_gpu_batch_variants.py goes past it)
+        plan = b.launch_plan()
+        assert (plan["coords"], plan["front_threads"], plan["ns"]) == (1, 1024, 3), plan
         for g in range(0, 256, 5):
             w = oracle_state(*streams[g])
             assert first_difference(b.state(g), w) is None, f"graph {g}"

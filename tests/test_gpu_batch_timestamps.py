@@ -24,9 +24,9 @@ tests/test_ts_shapes.py asserts, from the oracle alone, that each stream reaches
 branch in every size class; the states here come from the same cache.  Every test asserts
 fallbacks(), so no graph silently takes the other path.  Not reached: a bucket over 16
 rounds or more (the other half of kb_sort's packing condition); the widest here is 1."""
-import numpy as np
 import pytest
 
+from batch_variants import check_commits
 from ts_shapes import CASES, KINDS, WIDTHS, check_reach, oracle_case
 
 pytestmark = pytest.mark.gpu
@@ -66,18 +66,7 @@ def _check_states(b, graphs):
 
 def _check_commits(b, graphs):
     """As test_gpu_batch_commit.py's _check_commits: the delivered records against the oracle."""
-    for g, (c, k) in enumerate(graphs):
-        w = oracle_case(c, k)[2]
-        label = f"case {c} {k}"
-        cm = b.commits(g)
-        ids, counts = cm["ids"], cm["counts"]
-        assert len(ids) == len(w["order"]) == b.info(g)["ordered"], label
-        assert np.array_equal(ids, w["order"]), f"{label}: ids"
-        assert np.array_equal(counts, w["counts"]), f"{label}: counts"
-        assert ids.dtype == np.int32 and counts.dtype == np.int64
-        assert cm["rr"].dtype == np.int32 and cm["cts"].dtype == np.int64
-        assert np.array_equal(cm["rr"], np.asarray(w["rr"])[ids]), f"{label}: rr"
-        assert np.array_equal(cm["cts"], np.asarray(w["cts"])[ids]), f"{label}: cts"
+    check_commits(b, [oracle_case(c, k)[2] for c, k in graphs], [f"case {c} {k}" for c, k in graphs])
 
 
 @pytest.mark.parametrize("n", WIDTHS)

@@ -71,6 +71,8 @@ def test_monte_carlo_config5_batch_all_digests():
             b.add(d, calls)
         tot = b.run()
         assert b.fallbacks() == 0  # every graph in bulk: what the digests check is hge_batch_bulk.hip
+        plan = b.launch_plan()  # the instances of more than two graphs per compute unit
+        assert (plan["coords"], plan["front_threads"], plan["ns"], plan["sort_threads"]) == (2, 256, 2, 64), plan
         got = [b.state(g) for g in range(graphs)]
         bad = [g for g in range(graphs) if digest(got[g]) != ref["digests"][g]]
         assert not bad, f"graphs differing from the oracle digests: {bad[:16]}"
