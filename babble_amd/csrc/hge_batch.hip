@@ -41,6 +41,12 @@
 //
 // Everything on the path is integer; results are bit-exact with the oracle
 // (tests/test_gpu_batch.py, tests/test_gpu_mc.py: every graph's full-state digest).
+//
+// This file holds the kernels (with hge_batch_bulk.hip, hge_batch_gen.hip and
+// hge_batch_stats.hip).  The host side, struct hge_batch in parts by lifetime and the C
+// ABI, is hge_batch_host.hip, included at the end: one translation unit.  Which instance
+// of a kernel a run launches and where a graph lies in the pools are decided in
+// hge_batch_plan.h (host only, tested on the CPU).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,20 +61,11 @@
 
 #include "../../include/hge.h"
 #include "hge_hip.h"
+#include "hge_batch_plan.h"  // GDesc, the launch plan, the pools' layout
 
 namespace hgb {
 
 constexpr int32_t INF = 0x7fffffff;
-
-struct GDesc {
-  int64_t eo;    // first event of the graph in the per-event pools
-  int32_t E;     // accepted events
-  int32_t co;    // first call in the per-call pools
-  int32_t K;     // calls
-  int32_t ro;    // first round row in the per-round pools
-  int32_t Rcap;  // rounds the graph may reach (E / SM + 2)
-  int32_t pad;
-};
 
 // batch tables (device pointers); per-graph blocks are addressed through GDesc
 struct BT {
@@ -1464,1115 +1461,5 @@ __global__ __launch_bounds__(256, OCC) void kb_consensus(BT t) {
 
 }  // namespace hgb
 
-// ===========================================================================
-// host side
-// ===========================================================================
-using namespace hgb;
-
-namespace {
-
-using hge::DBuf;
-using hge::Error;
-
-// A host array of the commit stream: mapped pinned memory the kernels store to
-// (dev: its device-side address), or pageable memory that a copy fills after the run
-// when the pinned allocation fails.
-template <typename T>
-struct HostField {
-  T* h = nullptr;
-  T* dev = nullptr;
-  size_t cap = 0;
-  bool pinned = false;
-  void need(size_t n, bool try_pin) {
-    if (h && n <= cap) return;
-    pin_ = hge::PBuf<T>();
-    page_.reset();
-    h = dev = nullptr;
-    cap = 0;
-    pinned = false;
-    n = std::max<size_t>(n, 1);
-    if (try_pin) {
-      try {
-        pin_.need(n);
-        dev = hge::PinnedMem::device_ptr(pin_.p);
-      } catch (const Error&) {
-      }
-      if (dev) {
-        h = pin_.p;
-        pinned = true;
-      } else {
-        pin_ = hge::PBuf<T>();
-        (void)hipGetLastError();  // not an error of the run: the copy path takes over
-      }
-    }
-    if (!h) {
-      page_.reset(new (std::nothrow) T[n]);
-      if (!page_) throw Error{HGE_ERR_INTERNAL, "commit stream: host allocation failed"};
-      h = page_.get();
-    }
-    cap = n;
-  }
-
- private:
-  hge::PBuf<T> pin_;
-  std::unique_ptr<T[]> page_;
-};
-
-}  // namespace
-
-struct hge_batch {
-  int N = 0, SM = 1, device = 0, ncu = 256;
-  hge::Stream st;  // declared before every buffer and event: destroyed after them
-  hge::Event ev[9];
-  std::string err;
-  struct Graph {
-    std::vector<int32_t> cr, ix, sp, op, oc, ntx;
-    std::vector<int64_t> ts;
-    std::vector<uint64_t> S;
-    std::vector<uint8_t> coin;
-    std::vector<int64_t> calls;  // accepted counts at the call points
-    std::vector<std::vector<int32_t>> chain;
-  };
-  std::vector<Graph> gs;
-  bool staged = false, ran = false;
-  std::vector<GDesc> hd;
-  int64_t Etot = 0;
-  int64_t Ktot = 0, Rtot = 0;
-  int ccap = 0;
-  std::vector<int64_t> h_scal;
-  static constexpr int NK = 8;  // coords, fd, fdrows, front, fame (prep + pairs), fold (+ theta), receive, order
-  float kms[NK] = {};
-  // device tables
-  DBuf<GDesc> d_gd;
-  DBuf<int32_t> d_cr, d_ix, d_sp, d_op, d_oc, d_ntx, d_clen, d_chain, d_LA, d_FDT, d_FD, d_round, d_rr, d_W, d_WIX,
-      d_WFD;
-  DBuf<int32_t> d_rcnt, d_ver, d_thv, d_th, d_U, d_Ur, d_Ucp, d_order, d_krr, d_kid;
-  DBuf<int64_t> d_ts, d_tsch, d_calls, d_cts, d_counts, d_scal, d_kct;
-  DBuf<uint64_t> d_Sch;
-  DBuf<int32_t> d_ntxch;
-  DBuf<uint64_t> d_S, d_ssb, d_seeb, d_ks0;
-  DBuf<uint8_t> d_coin, d_wit, d_WCOIN;
-  DBuf<int8_t> d_fame;
-  DBuf<uint64_t> d_dbg;
-  bool dbg_on = getenv("HGB_STAMPS") != nullptr;
-  // the bulk call schedule; HGB_SERIAL=1 (test hook): every graph through kb_consensus
-  bool serial = getenv("HGB_SERIAL") != nullptr;
-  DBuf<int32_t> d_roundch, d_rrch, d_rslot, d_glist, d_cg, d_Rc, d_rfirst, d_rrank, d_xcall, d_gx, d_nivl, d_fsuf, d_thp, d_thR, d_rcall, d_bcnt, d_boff, d_wlc;
-  DBuf<uint64_t> d_arr, d_Dp, d_ivF, d_thF;
-  DBuf<int4> d_ivh;
-  DBuf<int4> d_wl;
-  DBuf<int2> d_cinf;
-  DBuf<int64_t> d_gctx, d_ctsch;
-  int Emax = 0;
-  int64_t n_fallback = 0;  // graphs the last run replayed through kb_consensus
-  // the kernel instances the last run chose from the batch's size (hge_batch_launch_plan):
-  // set where run_stages and run take their branches, 0 for a stage that did not launch
-  struct Plan {
-    int32_t nm = 0, coords = 0, front_threads = 0, ns = 0, sort_threads = 0, consensus_occ = 0, dlv = 0;
-  } plan;
-  // the commit stream in host memory (hge_batch_set_delivery), pooled like the device
-  // tables: ids / rr / cts at GDesc::eo, counts at GDesc::co
-  uint32_t deliver = 0;   // requested: bit 0 order and counts, bit 1 rr and cts as well
-  int32_t delivered = 0;  // the last run: 0 not delivered, 1 written by the kernels, 2 copied after the run
-  uint32_t delivered_what = 0;
-  bool no_pin = getenv("HGB_TEST_NO_PIN") != nullptr;  // test hook: take the copy path
-  HostField<int32_t> h_ids, h_orr;
-  HostField<int64_t> h_octs, h_counts;
-  DBuf<int32_t> d_orr;  // the copy path's device side of rr / cts (ids and counts: d_order, d_counts)
-  DBuf<int64_t> d_octs;
-  // generated graphs (hge_batch_generate, hge_batch_gen.hip): their parameters, and on
-  // the device the submission -> id map, the sizes the counting walk found, the raw
-  // submission pools and the accepted events' steps.  A batch holds these or `gs`.
-  std::vector<GenG> gen;
-  std::vector<int32_t> h_gcnt;
-  int64_t Stot = 0;
-  DBuf<GenG> d_gg;
-  DBuf<int32_t> d_gmap, d_gcnt, d_scr, d_six, d_ssp, d_sop, d_sstep, d_sst, d_sacc, d_estep;
-  DBuf<hge_event> d_raw;
-  // the statistics pass (hge_batch_stats, hge_batch_stats.hip): valid from a run until the
-  // batch changes; which graphs kb_consensus replayed (the source of an event's commit
-  // call), its table, and the pass's grow-only scratch and results
-  bool stats_ok = false;
-  std::vector<int32_t> h_path;
-  DBuf<int32_t> d_xcc, d_path;
-  DBuf<int64_t> d_spart, d_sout;
-  std::vector<int64_t> h_sout;
-
-  int graphs() const { return gen.empty() ? (int)gs.size() : (int)gen.size(); }
-
-  // the stream drained before the members die
-  ~hge_batch() {
-    if (st) (void)hipStreamSynchronize(st);
-  }
-
-  // sized from the staged pools; kept across runs
-  void ensure_delivery() {
-    if (!(deliver & 1)) return;
-    const size_t E1 = (size_t)std::max<int64_t>(Etot, 1), K1 = (size_t)std::max<int64_t>(Ktot, 1);
-    h_ids.need(E1, !no_pin);
-    h_counts.need(K1, !no_pin);
-    bool pin = h_ids.pinned && h_counts.pinned;
-    if (deliver & 2) {
-      h_orr.need(E1, !no_pin);
-      h_octs.need(E1, !no_pin);
-      pin = pin && h_orr.pinned && h_octs.pinned;
-      if (!pin) {
-        d_orr.need(E1);
-        d_octs.need(E1);
-      }
-    }
-  }
-  bool delivery_pinned() const {
-    return h_ids.pinned && h_counts.pinned && (!(deliver & 2) || (h_orr.pinned && h_octs.pinned));
-  }
-
-  // FromParentsLatest (hashgraph.go:366-396) and the index rule of the engine
-  // (hge_engine.hip admit: index-lying events are refused, HGE_ERR_INDEX)
-  int admit(Graph& G, const std::vector<int32_t>& last, const hge_event& e, int32_t sp, int32_t op) {
-    const int c = e.creator;
-    if (c < 0 || c >= N) return HGE_ERR_CREATOR;
-    const int known = (int)G.chain[c].size();
-    const int64_t E = (int64_t)G.cr.size();
-    if (sp == HGE_NONE && op == HGE_NONE && known == 0) return e.index == 0 ? HGE_OK : HGE_ERR_INDEX;
-    if (sp < 0 || sp >= E) return HGE_ERR_SELF_PARENT_UNKNOWN;
-    if (G.cr[sp] != c) return HGE_ERR_SELF_PARENT_CREATOR;
-    if (op < 0 || op >= E) return HGE_ERR_OTHER_PARENT_UNKNOWN;
-    if (sp != last[c]) return HGE_ERR_SELF_PARENT_NOT_LAST;
-    if (e.index != known) return HGE_ERR_INDEX;
-    return HGE_OK;
-  }
-
-  int add(const hge_event* ev, int64_t n_sub, const int64_t* cp, int64_t n_calls, int32_t* status) {
-    for (int64_t c = 0; c < n_calls; c++)
-      if (cp[c] < 1 || cp[c] > n_sub || (c > 0 && cp[c] <= cp[c - 1]))
-        throw Error{HGE_ERR_ARG, "hge_batch_add: call points must be strictly ascending within [1, n_sub]"};
-    if (n_sub >= INT32_MAX / 2) throw Error{HGE_ERR_ARG, "hge_batch_add: stream too long for a batch graph"};
-    if (!gen.empty()) throw Error{HGE_ERR_ARG, "hge_batch_add: the batch holds generated graphs (hge_batch_clear first)"};
-    gs.emplace_back();
-    Graph& G = gs.back();
-    G.chain.assign(N, {});
-    std::vector<int32_t> last(N, -1), idmap(n_sub, -1);
-    int64_t nc = 0;
-    for (int64_t i = 0; i < n_sub; i++) {
-      const int32_t s = ev[i].self_parent, o = ev[i].other_parent;
-      const int32_t sp = s < 0 ? HGE_NONE : (s < i && idmap[s] >= 0 ? idmap[s] : HGE_UNKNOWN);
-      const int32_t op = o < 0 ? HGE_NONE : (o < i && idmap[o] >= 0 ? idmap[o] : HGE_UNKNOWN);
-      const int r = admit(G, last, ev[i], sp, op);
-      if (r == HGE_OK) {
-        const int32_t id = (int32_t)G.cr.size();
-        idmap[i] = id;
-        G.cr.push_back(ev[i].creator);
-        G.ix.push_back(ev[i].index);
-        G.sp.push_back(sp);
-        G.op.push_back(op);
-        G.oc.push_back(op >= 0 ? G.cr[op] : 0);
-        G.ntx.push_back(ev[i].n_tx);
-        G.ts.push_back(ev[i].timestamp_ns);
-        for (int k = 0; k < 4; k++) {
-          uint64_t v = 0;
-          for (int b = 0; b < 8; b++) v = (v << 8) | ev[i].s[8 * k + b];
-          G.S.push_back(v);
-        }
-        G.coin.push_back(ev[i].hash[16] != 0);
-        G.chain[ev[i].creator].push_back(id);
-        last[ev[i].creator] = id;
-      }
-      if (status) status[i] = r == HGE_OK ? idmap[i] : r;
-      while (nc < n_calls && cp[nc] == i + 1) {
-        G.calls.push_back((int64_t)G.cr.size());
-        nc++;
-      }
-    }
-    staged = false;
-    ran = false;
-    stats_ok = false;
-    return (int)gs.size() - 1;
-  }
-
-  template <typename T>
-  void up(DBuf<T>& b, const std::vector<T>& h) {
-    b.need(h.size());
-    if (!h.empty()) HGE_HIPCHK(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  }
-
-  void stage() {
-    stats_ok = false;
-    if (staged) {
-      ensure_delivery();
-      return;
-    }
-    HGE_HIPCHK(hipSetDevice(device));
-    if (!gen.empty()) {
-      stage_generated();
-      return;
-    }
-    const int G = (int)gs.size();
-    hd.assign(G, GDesc{});
-    Etot = Ktot = Rtot = 0;
-    ccap = 1;
-    for (int g = 0; g < G; g++) {
-      const Graph& gr = gs[g];
-      GDesc& d = hd[g];
-      d.eo = Etot;
-      d.E = (int32_t)gr.cr.size();
-      d.co = (int32_t)Ktot;
-      d.K = (int32_t)gr.calls.size();
-      d.ro = (int32_t)Rtot;
-      // a round r + 1 exists only once >= SM witnesses of round r do: R <= E / SM + 1
-      d.Rcap = d.E / SM + 2;
-      Etot += d.E;
-      Ktot += d.K;
-      Rtot += d.Rcap;
-      for (int c = 0; c < N; c++) ccap = std::max(ccap, (int)gr.chain[c].size());
-    }
-    if (Rtot >= INT32_MAX || Ktot >= INT32_MAX) throw Error{HGE_ERR_CAPACITY, "batch too large"};
-    if (ccap >= (1 << 24)) throw Error{HGE_ERR_CAPACITY, "batch graph with a chain of 2^24 events or more"};
-    std::vector<int32_t> cr, ix, sp, op, oc, ntx, clen((size_t)G * N), chain((size_t)G * N * ccap, -1), cgv;
-    Emax = 0;
-    for (int g = 0; g < G; g++) {
-      cgv.insert(cgv.end(), (size_t)hd[g].K, g);
-      Emax = std::max(Emax, hd[g].E);
-    }
-    std::vector<int64_t> ts, tsch((size_t)G * N * ccap, 0), calls;
-    std::vector<uint64_t> Sch((size_t)G * N * ccap, 0);
-    std::vector<int32_t> ntxch((size_t)G * N * ccap, 0);
-    std::vector<uint64_t> S;
-    std::vector<uint8_t> coin;
-    cr.reserve(Etot);
-    for (int g = 0; g < G; g++) {
-      const Graph& gr = gs[g];
-      cr.insert(cr.end(), gr.cr.begin(), gr.cr.end());
-      ix.insert(ix.end(), gr.ix.begin(), gr.ix.end());
-      sp.insert(sp.end(), gr.sp.begin(), gr.sp.end());
-      op.insert(op.end(), gr.op.begin(), gr.op.end());
-      oc.insert(oc.end(), gr.oc.begin(), gr.oc.end());
-      ntx.insert(ntx.end(), gr.ntx.begin(), gr.ntx.end());
-      ts.insert(ts.end(), gr.ts.begin(), gr.ts.end());
-      S.insert(S.end(), gr.S.begin(), gr.S.end());
-      coin.insert(coin.end(), gr.coin.begin(), gr.coin.end());
-      calls.insert(calls.end(), gr.calls.begin(), gr.calls.end());
-      for (int c = 0; c < N; c++) {
-        clen[(size_t)g * N + c] = (int32_t)gr.chain[c].size();
-        for (size_t p = 0; p < gr.chain[c].size(); p++) {
-          chain[((size_t)g * N + c) * ccap + p] = gr.chain[c][p];
-          tsch[((size_t)g * N + c) * ccap + p] = gr.ts[gr.chain[c][p]];
-          Sch[((size_t)g * N + c) * ccap + p] = gr.S[4 * (size_t)gr.chain[c][p]];
-          ntxch[((size_t)g * N + c) * ccap + p] = gr.ntx[gr.chain[c][p]];
-        }
-      }
-    }
-    up(d_cr, cr);
-    up(d_ix, ix);
-    up(d_sp, sp);
-    up(d_op, op);
-    up(d_oc, oc);
-    up(d_ntx, ntx);
-    up(d_ts, ts);
-    up(d_S, S);
-    up(d_coin, coin);
-    up(d_calls, calls);
-    up(d_clen, clen);
-    up(d_chain, chain);
-    up(d_tsch, tsch);
-    up(d_Sch, Sch);
-    up(d_ntxch, ntxch);
-    up(d_cg, cgv);
-    d_gd.need(G);
-    HGE_HIPCHK(hipMemcpyAsync(d_gd.p, hd.data(), sizeof(GDesc) * G, hipMemcpyHostToDevice, st));
-    need_tables(G);
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    ensure_delivery();
-    staged = true;
-  }
-
-  void generate(const hge_gossip_params& p, int32_t n_graphs, uint64_t seed0) {
-    if (!gs.empty()) throw Error{HGE_ERR_ARG, "hge_batch_generate: the batch holds added graphs (hge_batch_clear first)"};
-    GenG q{};
-    q.tf = (uint64_t)(p.fork_p * 4294967296.0);
-    q.tc = (uint64_t)(p.cascade_p * 4294967296.0);
-    q.events = (int32_t)p.events;
-    q.k = std::min<int64_t>(p.k, 5 * p.events);  // past the stream's length: one call
-    q.forkers = p.forkers;
-    q.op_lag = p.op_lag;
-    for (int32_t i = 0; i < n_graphs; i++) {
-      q.seed = seed0 + (uint64_t)i;
-      gen.push_back(q);
-    }
-    staged = false;
-    ran = false;
-    stats_ok = false;
-  }
-
-  void clear() {
-    gs.clear();
-    gen.clear();
-    hd.clear();
-    staged = false;
-    ran = false;
-    stats_ok = false;
-    delivered = 0;
-    n_fallback = 0;
-    plan = Plan{};
-  }
-
-  GenT gen_tables() const {
-    GenT t{};
-    t.N = N;
-    t.ccap = ccap;
-    t.gg = d_gg.p;
-    t.gd = d_gd.p;
-    t.map = d_gmap.p;
-    t.cnt = d_gcnt.p;
-    t.s_cr = d_scr.p;
-    t.s_ix = d_six.p;
-    t.s_sp = d_ssp.p;
-    t.s_op = d_sop.p;
-    t.s_step = d_sstep.p;
-    t.s_st = d_sst.p;
-    t.s_acc = d_sacc.p;
-    t.cr = d_cr.p;
-    t.ix = d_ix.p;
-    t.sp = d_sp.p;
-    t.op = d_op.p;
-    t.oc = d_oc.p;
-    t.ntx = d_ntx.p;
-    t.estep = d_estep.p;
-    t.clen = d_clen.p;
-    t.chain = d_chain.p;
-    t.ntxch = d_ntxch.p;
-    t.cg = d_cg.p;
-    t.ts = d_ts.p;
-    t.tsch = d_tsch.p;
-    t.calls = d_calls.p;
-    t.S = d_S.p;
-    t.Sch = d_Sch.p;
-    t.coin = d_coin.p;
-    return t;
-  }
-
-  // The generated graphs' staging: what stage() uploads, written by kernels.  The pools'
-  // offsets need every graph's submission, accepted and call counts and the longest
-  // chain: a counting instance of the walk finds them (the walk is deterministic), one
-  // readback of 16 bytes per graph brings them to the host, and the walk runs again
-  // into pools laid out exactly.  An upper bound instead (5 submissions a step, all
-  // accepted, one chain) would size the E x N and chain tables of every later stage
-  // five and N times too large.
-  void stage_generated() {
-    const int G = (int)gen.size();
-    int64_t mtot = 0;
-    for (GenG& q : gen) {
-      q.mo = mtot;
-      q.so = 0;
-      mtot += 5 * (int64_t)q.events;
-    }
-    d_gg.need(G);
-    d_gcnt.need((size_t)G * 4);
-    d_gmap.need((size_t)mtot);
-    HGE_HIPCHK(hipMemcpyAsync(d_gg.p, gen.data(), sizeof(GenG) * G, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kg_walk<false>, dim3(G), dim3(64), 0, st, gen_tables());
-    HGE_HIPCHK(hipGetLastError());
-    h_gcnt.resize((size_t)G * 4);
-    HGE_HIPCHK(hipMemcpyAsync(h_gcnt.data(), d_gcnt.p, (size_t)G * 16, hipMemcpyDeviceToHost, st));
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    hd.assign(G, GDesc{});
-    Etot = Ktot = Rtot = Stot = 0;
-    ccap = 1;
-    Emax = 0;
-    int Kmax = 0;
-    for (int g = 0; g < G; g++) {
-      const int64_t nsub = h_gcnt[(size_t)g * 4], k = gen[g].k;
-      GDesc& d = hd[g];
-      d.eo = Etot;
-      d.E = h_gcnt[(size_t)g * 4 + 1];
-      d.co = (int32_t)Ktot;
-      d.K = (int32_t)((nsub + k - 1) / k);
-      d.ro = (int32_t)Rtot;
-      d.Rcap = d.E / SM + 2;
-      gen[g].so = Stot;
-      Etot += d.E;
-      Ktot += d.K;
-      Rtot += d.Rcap;
-      Stot += nsub;
-      ccap = std::max(ccap, (int)h_gcnt[(size_t)g * 4 + 2]);
-      Emax = std::max(Emax, d.E);
-      Kmax = std::max(Kmax, d.K);
-      if (Rtot >= INT32_MAX || Ktot >= INT32_MAX) throw Error{HGE_ERR_CAPACITY, "batch too large"};
-    }
-    HGE_HIPCHK(hipMemcpyAsync(d_gg.p, gen.data(), sizeof(GenG) * G, hipMemcpyHostToDevice, st));
-    d_gd.need(G);
-    HGE_HIPCHK(hipMemcpyAsync(d_gd.p, hd.data(), sizeof(GDesc) * G, hipMemcpyHostToDevice, st));
-    const size_t E1 = (size_t)std::max<int64_t>(Etot, 1), K1 = (size_t)std::max<int64_t>(Ktot, 1);
-    const size_t S1 = (size_t)std::max<int64_t>(Stot, 1), CH = (size_t)G * N * ccap;
-    for (DBuf<int32_t>* b : {&d_cr, &d_ix, &d_sp, &d_op, &d_oc, &d_ntx, &d_estep}) b->need(E1);
-    for (DBuf<int32_t>* b : {&d_scr, &d_six, &d_ssp, &d_sop, &d_sstep, &d_sst, &d_sacc}) b->need(S1);
-    d_ts.need(E1);
-    d_S.need(4 * E1);
-    d_coin.need(E1);
-    d_calls.need(K1);
-    d_cg.need(K1);
-    d_clen.need((size_t)G * N);
-    d_chain.need(CH);
-    d_tsch.need(CH);
-    d_Sch.need(CH);
-    d_ntxch.need(CH);
-    // the chain tables past a chain's length, as stage() uploads them
-    HGE_HIPCHK(hipMemsetAsync(d_chain.p, 0xFF, CH * 4, st));
-    HGE_HIPCHK(hipMemsetAsync(d_tsch.p, 0, CH * 8, st));
-    HGE_HIPCHK(hipMemsetAsync(d_Sch.p, 0, CH * 8, st));
-    HGE_HIPCHK(hipMemsetAsync(d_ntxch.p, 0, CH * 4, st));
-    const GenT t = gen_tables();
-    hipLaunchKernelGGL(kg_walk<true>, dim3(G), dim3(64), 0, st, t);
-    HGE_HIPCHK(hipGetLastError());
-    const int fx = (std::max(Emax, Kmax) + 255) / 256;
-    if (fx > 0) {
-      hipLaunchKernelGGL(kg_fill, dim3((unsigned)fx, (unsigned)G), dim3(256), 0, st, t);
-      HGE_HIPCHK(hipGetLastError());
-    }
-    need_tables(G);
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    ensure_delivery();
-    staged = true;
-  }
-
-  // graph g's raw stream and admission results, read back from the staged pools
-  int64_t submissions(int32_t g, hge_event* ev_out, int32_t* status_out, int64_t cap) {
-    if (gen.empty() || !staged) throw Error{HGE_ERR_ARG, "hge_batch_submissions: no staged generated graphs"};
-    const int64_t nsub = h_gcnt[(size_t)g * 4];
-    if (cap < nsub || nsub == 0) return nsub;
-    HGE_HIPCHK(hipSetDevice(device));
-    if (ev_out) {
-      d_raw.need((size_t)nsub);
-      hipLaunchKernelGGL(kg_raw, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, gen_tables(), g, d_raw.p);
-      HGE_HIPCHK(hipGetLastError());
-      HGE_HIPCHK(hipMemcpyAsync(ev_out, d_raw.p, (size_t)nsub * sizeof(hge_event), hipMemcpyDeviceToHost, st));
-    }
-    if (status_out)
-      HGE_HIPCHK(hipMemcpyAsync(status_out, d_sst.p + gen[g].so, (size_t)nsub * 4, hipMemcpyDeviceToHost, st));
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    return nsub;
-  }
-
-  // the tables a run writes, sized from the staged pools (hd, Etot, Ktot, Rtot, ccap)
-  void need_tables(int G) {
-    const size_t E1 = (size_t)std::max<int64_t>(Etot, 1);
-    d_LA.need(E1 * N);
-    d_FDT.need((size_t)G * N * N * ccap);
-    d_FD.need((size_t)G * N * ccap * N);
-    d_round.need(E1);
-    d_wit.need(E1);
-    d_rr.need(E1);
-    d_cts.need(E1);
-    d_U.need(E1);
-    d_Ur.need(E1);
-    d_Ucp.need(E1);
-    d_order.need(E1);
-    d_krr.need(2 * E1 + 64);
-    d_kct.need(2 * E1 + 64);
-    d_ks0.need(2 * E1 + 64);
-    d_kid.need(2 * E1 + 64);
-    const size_t RN = (size_t)std::max<int64_t>(Rtot, 1) * N;
-    d_W.need(RN);
-    d_WIX.need(RN);
-    d_WFD.need(RN * N);
-    d_WCOIN.need(RN);
-    d_ssb.need(RN);
-    d_seeb.need(RN);
-    d_fame.need(RN);
-    d_th.need(RN);
-    d_rcnt.need(RN / N);
-    d_ver.need(RN / N);
-    d_thv.need(RN / N);
-    d_counts.need(std::max<int64_t>(Ktot, 1));
-    d_scal.need((size_t)G * 8);
-    if (dbg_on) d_dbg.need((size_t)G * 8);
-    const size_t K1 = (size_t)std::max<int64_t>(Ktot, 1);
-    d_glist.need(G);
-    d_Rc.need(K1);
-    d_rfirst.need(RN / N);
-    d_xcall.need(E1);
-    d_arr.need(E1);
-    d_Dp.need(K1 * BNS * 2);
-    d_gx.need((size_t)G * 16);
-    d_ivh.need(RN / N * BVCAP);
-    d_ivF.need(RN / N * BVCAP);
-    d_nivl.need(RN / N);
-    d_fsuf.need(RN / N);
-    d_thp.need((size_t)G * BICAP * N);
-    d_thR.need((size_t)G * BICAP);
-    d_thF.need((size_t)G * BICAP);
-    const size_t CH = (size_t)G * N * ccap;
-    d_roundch.need(CH);
-    d_rcall.need(CH);
-    d_rrank.need(CH);
-    d_rrch.need(CH);
-    d_rslot.need(CH);
-    d_ctsch.need(CH);
-    d_bcnt.need(K1);
-    d_boff.need(K1);
-    d_wl.need(K1);
-    d_wlc.need(1);
-    d_gctx.need(G);
-    d_cinf.need(E1);
-    d_xcc.need(E1);
-  }
-
-  BT tables() const {
-    BT t;
-    t.N = N;
-    t.SM = SM;
-    t.ccap = ccap;
-    t.gd = d_gd.p;
-    t.cr = d_cr.p;
-    t.ix = d_ix.p;
-    t.sp = d_sp.p;
-    t.op = d_op.p;
-    t.oc = d_oc.p;
-    t.ntx = d_ntx.p;
-    t.clen = d_clen.p;
-    t.ts = d_ts.p;
-    t.S = d_S.p;
-    t.coin = d_coin.p;
-    t.chain = d_chain.p;
-    t.tsch = d_tsch.p;
-    t.calls = d_calls.p;
-    t.LA = d_LA.p;
-    t.FDT = d_FDT.p;
-    t.FD = d_FD.p;
-    t.Sch = d_Sch.p;
-    t.ntxch = d_ntxch.p;
-    t.round = d_round.p;
-    t.wit = d_wit.p;
-    t.rr = d_rr.p;
-    t.cts = d_cts.p;
-    t.W = d_W.p;
-    t.WIX = d_WIX.p;
-    t.WFD = d_WFD.p;
-    t.WCOIN = d_WCOIN.p;
-    t.ssb = d_ssb.p;
-    t.seeb = d_seeb.p;
-    t.fame = d_fame.p;
-    t.rcnt = d_rcnt.p;
-    t.ver = d_ver.p;
-    t.thv = d_thv.p;
-    t.th = d_th.p;
-    t.U = d_U.p;
-    t.Ur = d_Ur.p;
-    t.Ucp = d_Ucp.p;
-    t.order = d_order.p;
-    t.counts = d_counts.p;
-    t.ord_rr = nullptr;
-    t.ord_cts = nullptr;
-    t.scal = d_scal.p;
-    t.krr = d_krr.p;
-    t.kct = d_kct.p;
-    t.ks0 = d_ks0.p;
-    t.kid = d_kid.p;
-    t.dbg = dbg_on ? d_dbg.p : nullptr;
-    t.glist = nullptr;
-    t.cg = d_cg.p;
-    t.Rc = d_Rc.p;
-    t.rfirst = d_rfirst.p;
-    t.xcall = d_xcall.p;
-    t.arr = d_arr.p;
-    t.Dp = d_Dp.p;
-    t.gx = d_gx.p;
-    t.ivh = d_ivh.p;
-    t.ivF = d_ivF.p;
-    t.nivl = d_nivl.p;
-    t.fsuf = d_fsuf.p;
-    t.thp = d_thp.p;
-    t.thR = d_thR.p;
-    t.thF = d_thF.p;
-    t.roundch = d_roundch.p;
-    t.rcall = d_rcall.p;
-    t.rrank = d_rrank.p;
-    t.rrch = d_rrch.p;
-    t.rslot = d_rslot.p;
-    t.ctsch = d_ctsch.p;
-    t.bcnt = d_bcnt.p;
-    t.boff = d_boff.p;
-    t.wl = d_wl.p;
-    t.wlc = d_wlc.p;
-    t.gctx = d_gctx.p;
-    t.cinf = d_cinf.p;
-    t.xcc = d_xcc.p;
-    return t;
-  }
-
-  template <typename K>
-  void launch(K kern, int G, const BT& t, int block = 64) {
-    hipLaunchKernelGGL(kern, dim3(G), dim3(block), 0, st, t);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw Error{HGE_ERR_DEVICE, std::string("batch launch: ") + hipGetErrorString(e)};
-  }
-
-  template <int NM, bool DLV>
-  void run_stages(int G, const BT& t) {
-    plan.nm = NM;
-    plan.dlv = DLV;
-    // a workgroup of 1,024 threads per graph while two fit a CU, else 512
-    // 1,024 threads per graph and the kb_levels pass while two graphs fit a CU, else
-    // 512 threads levelling their own chunks
-    if (G <= 2 * ncu) {
-      if (Emax > 0) {
-        hipLaunchKernelGGL(kb_levels, dim3((unsigned)((Emax + 255) / 256), (unsigned)G), dim3(256), 0, st, t);
-        HGE_HIPCHK(hipGetLastError());
-      }
-      // the columns split over two workgroups while both still get a CU of their own
-      // (128 graphs: 0.46 -> 0.43 ms; at 256 graphs, two per CU, 0.49 -> 0.51; four
-      // 8-column parts: 0.45 / 0.55)
-      plan.coords = 2 * G <= ncu ? 0 : 1;
-      if (2 * G <= ncu) hipLaunchKernelGGL((kb_coords<NM, 512, true, 2>), dim3(G * 2), dim3(512), 0, st, t);
-      else launch(kb_coords<NM, 1024, true>, G, t, 1024);
-      HGE_HIPCHK(hipGetLastError());
-    } else {
-      plan.coords = 2;
-      launch(kb_coords<NM, 512, false>, G, t, 512);
-    }
-    HGE_HIPCHK(hipEventRecord(ev[1], st));
-    launch(kb_fd<NM>, G * N, t, 64 * (NM / FCW));
-    HGE_HIPCHK(hipEventRecord(ev[2], st));
-    launch(kb_fdrows<NM>, G * N, t, 256);  // rows for kb_front (kb_median reads the run layout)
-    HGE_HIPCHK(hipEventRecord(ev[3], st));
-    plan.front_threads = G > 2 * ncu ? 256 : G > ncu ? 512 : 1024;
-    if (G > 2 * ncu) launch(kb_front<NM, 256>, G, t, 256);
-    else if (G > ncu) launch(kb_front<NM, 512>, G, t, 512);
-    else launch(kb_front<NM, 1024>, G, t, 1024);
-    HGE_HIPCHK(hipEventRecord(ev[4], st));
-    if (serial) {  // every graph through kb_consensus, after the run's readback
-      for (int k = 5; k < 9; k++) HGE_HIPCHK(hipEventRecord(ev[k], st));
-      return;
-    }
-    launch(kb_prep<NM>, G, t, 1024);
-    plan.ns = G > 2 * ncu ? 2 : 3;
-    if (G > 2 * ncu) hipLaunchKernelGGL((kb_pairs<NM, 2>), dim3(8, (unsigned)G), dim3(256), 0, st, t);
-    else hipLaunchKernelGGL((kb_pairs<NM, 3>), dim3(8, (unsigned)G), dim3(256), 0, st, t);
-    HGE_HIPCHK(hipGetLastError());
-    HGE_HIPCHK(hipEventRecord(ev[5], st));
-    if (G > 2 * ncu) launch((kb_fold<NM, 2>), G, t, 64);
-    else launch((kb_fold<NM, 3>), G, t, 64);
-    launch(kb_theta<NM>, G, t, 256);
-    HGE_HIPCHK(hipEventRecord(ev[6], st));
-    if (Emax > 0) {
-      hipLaunchKernelGGL(kb_receive<NM>, dim3((unsigned)N, (unsigned)G), dim3(256), 0, st, t);
-      HGE_HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(kb_median<NM>, dim3((unsigned)(N * ((ccap + 255) / 256)), (unsigned)G), dim3(256), 0, st, t);
-      HGE_HIPCHK(hipGetLastError());
-    }
-    HGE_HIPCHK(hipEventRecord(ev[7], st));
-    launch(kb_order_prep<NM>, G, t, 1024);
-    // call buckets: up to 1,024 keys one wave each (a workgroup of four while the
-    // batch has few buckets), larger ones a workgroup each
-    const int nbk = (int)std::min<int64_t>(std::max<int64_t>(Ktot, 1), (int64_t)ncu * 16);
-    plan.sort_threads = Ktot > 16 * (int64_t)ncu ? 64 : 256;
-    if (Ktot > 16 * (int64_t)ncu) hipLaunchKernelGGL((kb_sort<64, 0, 1024, DLV>), dim3(nbk), dim3(64), 0, st, t, 0);
-    else hipLaunchKernelGGL((kb_sort<256, 0, 1024, DLV>), dim3(nbk), dim3(256), 0, st, t, 0);
-    HGE_HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL((kb_sort<256, 1024, 4096, DLV>), dim3(ncu), dim3(256), 0, st, t, 1);
-    HGE_HIPCHK(hipGetLastError());
-    HGE_HIPCHK(hipEventRecord(ev[8], st));
-  }
-
-  int64_t run() {
-    stage();
-    delivered = 0;
-    plan = Plan{};
-    const int G = graphs();
-    if (G == 0) {
-      h_path.clear();
-      stats_ok = true;
-      return 0;
-    }
-    const size_t RN = (size_t)std::max<int64_t>(Rtot, 1) * N;
-    const size_t E1 = (size_t)std::max<int64_t>(Etot, 1);
-    const size_t K1 = (size_t)std::max<int64_t>(Ktot, 1);
-    ClrList cl{};
-    auto seg = [&](void* p, size_t bytes, uint32_t pat) { cl.s[cl.n++] = ClrSeg{p, (uint64_t)bytes, pat}; };
-    seg(d_W.p, RN * 4, ~0u);
-    seg(d_WIX.p, RN * 4, ~0u);
-    seg(d_ssb.p, RN * 8, 0);
-    seg(d_seeb.p, RN * 8, 0);
-    seg(d_fame.p, RN, 0);
-    seg(d_rcnt.p, RN / N * 4, 0);
-    seg(d_ver.p, RN / N * 4, 0);
-    seg(d_thv.p, RN / N * 4, ~0u);
-    seg(d_rr.p, E1 * 4, ~0u);
-    seg(d_cts.p, E1 * 8, 0);
-    seg(d_scal.p, (size_t)G * 64, 0);
-    seg(d_bcnt.p, K1 * 4, 0);
-    seg(d_wlc.p, 4, 0);
-    seg(d_gctx.p, (size_t)G * 8, 0);
-    hipLaunchKernelGGL(kb_clear, dim3((unsigned)std::min<size_t>(2048, (E1 * 8 / 16 + 255) / 256 + 1)), dim3(256), 0, st, cl);
-    HGE_HIPCHK(hipGetLastError());
-    BT t = tables();
-    // delivery: the sorts and kb_consensus store the commit stream into mapped host
-    // memory (the fallback pass below into the same slots); it is the host's after the
-    // run's last synchronise
-    const int mode = !(deliver & 1) ? 0 : delivery_pinned() ? 1 : 2;
-    if (mode == 1) {
-      t.order = h_ids.dev;
-      t.counts = h_counts.dev;
-    }
-    if (mode && (deliver & 2)) {
-      t.ord_rr = mode == 1 ? h_orr.dev : d_orr.p;
-      t.ord_cts = mode == 1 ? h_octs.dev : d_octs.p;
-    }
-    HGE_HIPCHK(hipEventRecord(ev[0], st));
-    const bool dlv = t.ord_rr != nullptr;  // the kernel instances that store rr / cts in commit order
-    if (N <= 32) dlv ? run_stages<32, true>(G, t) : run_stages<32, false>(G, t);
-    else dlv ? run_stages<64, true>(G, t) : run_stages<64, false>(G, t);
-    h_scal.resize((size_t)G * 8);
-    HGE_HIPCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < NK; k++) HGE_HIPCHK(hipEventElapsedTime(&kms[k], ev[k], ev[k + 1]));
-    // graphs the bulk fold could not hold: replayed by kb_consensus (their outputs untouched so far)
-    std::vector<int32_t> fb;
-    for (int g = 0; g < G; g++)
-      if (serial || (h_scal[(size_t)g * 8 + 7] && !h_scal[(size_t)g * 8 + 6])) fb.push_back(g);
-    n_fallback = (int64_t)fb.size();
-    h_path.assign((size_t)G, 0);
-    for (int32_t g : fb) h_path[(size_t)g] = 1;
-    if (!fb.empty()) {
-      HGE_HIPCHK(hipMemcpyAsync(d_glist.p, fb.data(), fb.size() * 4, hipMemcpyHostToDevice, st));
-      t.glist = d_glist.p;
-      const int F = (int)fb.size();
-      plan.consensus_occ = F > 2 * ncu ? 4 : 1;
-      float ms = 0;
-      HGE_HIPCHK(hipEventRecord(ev[7], st));
-      auto replay = [&](auto kern_off, auto kern_on) {
-        dlv ? launch(kern_on, F, t, 256) : launch(kern_off, F, t, 256);
-      };
-      if (N <= 32) {
-        if (F > 2 * ncu) replay(kb_consensus<32, 4, false>, kb_consensus<32, 4, true>);
-        else replay(kb_consensus<32, 1, false>, kb_consensus<32, 1, true>);
-      } else {
-        if (F > 2 * ncu) replay(kb_consensus<64, 4, false>, kb_consensus<64, 4, true>);
-        else replay(kb_consensus<64, 1, false>, kb_consensus<64, 1, true>);
-      }
-      HGE_HIPCHK(hipEventRecord(ev[8], st));
-      HGE_HIPCHK(hipMemcpyAsync(h_scal.data(), d_scal.p, (size_t)G * 64, hipMemcpyDeviceToHost, st));
-      HGE_HIPCHK(hipStreamSynchronize(st));
-      HGE_HIPCHK(hipEventElapsedTime(&ms, ev[7], ev[8]));
-      kms[NK - 1] += ms;
-    }
-    if (dbg_on) {  // section cycles of kb_consensus, summed over the graphs
-      std::vector<uint64_t> hd_((size_t)G * 8);
-      HGE_HIPCHK(hipMemcpy(hd_.data(), d_dbg.p, (size_t)G * 64, hipMemcpyDeviceToHost));
-      double sum[5] = {};
-      for (int g = 0; g < G; g++)
-        for (int i = 0; i < 5; i++) sum[i] += (double)hd_[(size_t)g * 8 + i];
-      fprintf(stderr, "[hgb stamps] per graph cycles: divide %.0f fame %.0f thresholds %.0f receive %.0f order %.0f\n",
-              sum[0] / G, sum[1] / G, sum[2] / G, sum[3] / G, sum[4] / G);
-    }
-    int64_t tot = 0;
-    for (int g = 0; g < G; g++) {
-      if (h_scal[(size_t)g * 8 + 6])
-        throw Error{HGE_ERR_INTERNAL, "batch graph " + std::to_string(g) + ": round capacity exceeded"};
-      tot += h_scal[(size_t)g * 8 + 4];
-    }
-    if (mode == 2) {  // no pinned memory: one pooled copy per field
-      HGE_HIPCHK(hipMemcpy(h_ids.h, d_order.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
-      HGE_HIPCHK(hipMemcpy(h_counts.h, d_counts.p, (size_t)Ktot * 8, hipMemcpyDeviceToHost));
-      if (deliver & 2) {
-        HGE_HIPCHK(hipMemcpy(h_orr.h, d_orr.p, (size_t)Etot * 4, hipMemcpyDeviceToHost));
-        HGE_HIPCHK(hipMemcpy(h_octs.h, d_octs.p, (size_t)Etot * 8, hipMemcpyDeviceToHost));
-      }
-    }
-    delivered = mode;
-    delivered_what = deliver;
-    ran = true;
-    stats_ok = true;
-    return tot;
-  }
-
-  // The last run's statistics: three launches over the state in HBM, one copy, one wait.
-  // A graph is cut into nb spans while the batch alone would leave compute units idle.
-  void stats(const hge_stats_spec& s, int64_t* rows, int64_t* hist, int64_t* ghist) {
-    const int G = graphs();
-    const int64_t HL = hge_stats::hist_len(s);
-    if (G == 0) {
-      memset(hist, 0, (size_t)HL * 8);
-      return;
-    }
-    HGE_HIPCHK(hipSetDevice(device));
-    const int64_t per = (4 * (int64_t)ncu + G - 1) / G, cut = ((int64_t)Emax + 4095) / 4096;
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(per, cut), 1024));
-    const int64_t C = KS_ROW + HL;
-    d_spart.need((size_t)G * nb * C);
-    d_sout.need((size_t)(HL + (int64_t)G * C));
-    d_path.need((size_t)G);
-    HGE_HIPCHK(hipMemcpyAsync(d_path.p, h_path.data(), (size_t)G * 4, hipMemcpyHostToDevice, st));
-    ST t{};
-    t.s = s;
-    t.N = N;
-    t.ccap = ccap;
-    t.G = G;
-    t.nb = nb;
-    t.span = std::max<int64_t>(1, ((int64_t)Emax + nb - 1) / nb);
-    t.gd = d_gd.p;
-    t.round = d_round.p;
-    t.rr = d_rr.p;
-    t.cr = d_cr.p;
-    t.ix = d_ix.p;
-    t.rcall = d_rcall.p;
-    t.xcc = d_xcc.p;
-    t.W = d_W.p;
-    t.path = d_path.p;
-    t.cts = d_cts.p;
-    t.ts = d_ts.p;
-    t.calls = d_calls.p;
-    t.scal = d_scal.p;
-    t.fame = d_fame.p;
-    t.part = d_spart.p;
-    t.out = d_sout.p;
-    hipLaunchKernelGGL(ks_events, dim3((unsigned)nb, (unsigned)G), dim3(KS_NT), 0, st, t);
-    HGE_HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(ks_finish, dim3((unsigned)G), dim3(KS_NT), 0, st, t);
-    HGE_HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(ks_total, dim3((unsigned)((HL + 63) / 64)), dim3(1024), 0, st, t);
-    HGE_HIPCHK(hipGetLastError());
-    // totals | rows | slabs: the prefix the caller asked for
-    const size_t n = (size_t)(HL + (rows || ghist ? (int64_t)G * KS_ROW : 0) + (ghist ? (int64_t)G * HL : 0));
-    h_sout.resize(n);
-    HGE_HIPCHK(hipMemcpyAsync(h_sout.data(), d_sout.p, n * 8, hipMemcpyDeviceToHost, st));
-    HGE_HIPCHK(hipStreamSynchronize(st));
-    memcpy(hist, h_sout.data(), (size_t)HL * 8);
-    if (rows) memcpy(rows, h_sout.data() + HL, (size_t)G * KS_ROW * 8);
-    if (ghist) memcpy(ghist, h_sout.data() + HL + (size_t)G * KS_ROW, (size_t)G * HL * 8);
-  }
-
-  template <typename T>
-  void down(T* host, const T* dev, size_t n) {
-    if (host && n) HGE_HIPCHK(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
-  }
-};
-
-#define BGUARD_BEGIN try {
-#define BGUARD_END(b)                 \
-  }                                   \
-  catch (Error & e) {                 \
-    (b)->err = e.msg;                 \
-    return e.code;                    \
-  }                                   \
-  catch (std::exception & e) {        \
-    (b)->err = e.what();              \
-    return HGE_ERR_INTERNAL;          \
-  }
-
-extern "C" {
-
-int hge_batch_create(int32_t n_participants, int32_t device, hge_batch** out) {
-  if (!out || n_participants < 1 || n_participants > 64) return HGE_ERR_ARG;
-  hge_batch* b = new hge_batch();
-  b->N = n_participants;
-  b->SM = 2 * n_participants / 3 + 1;  // hashgraph.go:78-80
-  b->device = device;
-  try {
-    HGE_HIPCHK(hipSetDevice(device));
-    HGE_HIPCHK(hipDeviceGetAttribute(&b->ncu, hipDeviceAttributeMultiprocessorCount, device));
-    b->st.create();
-    for (auto& e : b->ev) e.create();
-  } catch (Error& e) {
-    delete b;
-    return e.code;
-  }
-  *out = b;
-  return HGE_OK;
-}
-
-void hge_batch_destroy(hge_batch* b) {
-  delete b;
-}
-
-const char* hge_batch_last_error(hge_batch* b) { return b ? b->err.c_str() : "null handle"; }
-
-int hge_batch_add(hge_batch* b, const hge_event* ev, int64_t n_sub, const int64_t* call_points, int64_t n_calls,
-                  int32_t* status_out, int32_t* graph_out) {
-  if (!b) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  if (n_sub < 0 || (n_sub > 0 && !ev) || n_calls < 0 || (n_calls > 0 && !call_points))
-    throw Error{HGE_ERR_ARG, "hge_batch_add: bad argument"};
-  const int g = b->add(ev, n_sub, call_points, n_calls, status_out);
-  if (graph_out) *graph_out = g;
-  return HGE_OK;
-  BGUARD_END(b)
-}
-
-int hge_batch_stage(hge_batch* b) {
-  if (!b) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  b->stage();
-  return HGE_OK;
-  BGUARD_END(b)
-}
-
-int hge_batch_run(hge_batch* b, int64_t* n_ordered) {
-  if (!b) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  const int64_t m = b->run();
-  if (n_ordered) *n_ordered = m;
-  return HGE_OK;
-  BGUARD_END(b)
-}
-
-int32_t hge_batch_graphs(hge_batch* b) { return b ? (int32_t)b->graphs() : -1; }
-
-int hge_batch_info(hge_batch* b, int32_t g, int64_t* info) {
-  if (!b || !info || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
-  if (!b->ran) {
-    b->err = "hge_batch_info: no replay yet (hge_batch_run)";
-    return HGE_ERR_ARG;
-  }
-  const int64_t* s = &b->h_scal[(size_t)g * 8];
-  info[0] = b->hd[g].E;  // the staged graph's: generated graphs have no host mirror
-  info[1] = b->hd[g].K;
-  for (int k = 0; k < 6; k++) info[2 + k] = s[k];
-  return HGE_OK;
-}
-
-int hge_batch_results(hge_batch* b, int32_t g, int32_t* order, int64_t* counts, int32_t* round, uint8_t* witness,
-                      int32_t* rr, int64_t* cts, int8_t* fame, int32_t* undetermined) {
-  if (!b || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  if (!b->ran) throw Error{HGE_ERR_ARG, "hge_batch_results: no replay yet (hge_batch_run)"};
-  const GDesc& d = b->hd[g];
-  const int64_t* s = &b->h_scal[(size_t)g * 8];
-  const int N = b->N;
-  if (b->delivered) {  // the last run delivered them: they are in host memory already
-    if (order && s[4]) memcpy(order, b->h_ids.h + d.eo, (size_t)s[4] * sizeof(int32_t));
-    if (counts && d.K) memcpy(counts, b->h_counts.h + d.co, (size_t)d.K * sizeof(int64_t));
-  } else {
-    b->down(order, b->d_order.p + d.eo, (size_t)s[4]);
-    b->down(counts, b->d_counts.p + d.co, (size_t)d.K);
-  }
-  b->down(round, b->d_round.p + d.eo, (size_t)d.E);
-  b->down(witness, b->d_wit.p + d.eo, (size_t)d.E);
-  b->down(rr, b->d_rr.p + d.eo, (size_t)d.E);
-  b->down(cts, b->d_cts.p + d.eo, (size_t)d.E);
-  b->down(undetermined, b->d_U.p + d.eo, (size_t)s[5]);
-  if (fame && s[0] > 0) {
-    const size_t RN = (size_t)s[0] * N;
-    std::vector<int32_t> w(RN);
-    std::vector<int8_t> f(RN);
-    b->down(w.data(), b->d_W.p + (size_t)d.ro * N, RN);
-    b->down(f.data(), b->d_fame.p + (size_t)d.ro * N, RN);
-    for (size_t k = 0; k < RN; k++) fame[k] = w[k] >= 0 ? f[k] : (int8_t)-1;
-  }
-  return HGE_OK;
-  BGUARD_END(b)
-}
-
-int64_t hge_batch_fallbacks(hge_batch* b) { return b ? b->n_fallback : -1; }
-
-int hge_batch_set_delivery(hge_batch* b, uint32_t what) {
-  if (!b) return HGE_ERR_ARG;
-  if (what > 3 || what == 2) {
-    b->err = "hge_batch_set_delivery: what is 0, 1 or 3 (bit 1 needs bit 0)";
-    return HGE_ERR_ARG;
-  }
-  b->deliver = what;
-  return HGE_OK;
-}
-
-int32_t hge_batch_delivery(hge_batch* b) { return b && b->ran ? b->delivered : 0; }
-
-int hge_batch_commits_view(hge_batch* b, int32_t g, hge_batch_commits* out) {
-  if (!b || !out || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
-  if (!b->ran || !b->delivered) {
-    b->err = "hge_batch_commits_view: the last run did not deliver (hge_batch_set_delivery, then hge_batch_run)";
-    return HGE_ERR_ARG;
-  }
-  const GDesc& d = b->hd[g];
-  const bool rec = (b->delivered_what & 2) != 0;
-  out->ids = b->h_ids.h + d.eo;
-  out->rr = rec ? b->h_orr.h + d.eo : nullptr;
-  out->cts = rec ? b->h_octs.h + d.eo : nullptr;
-  out->counts = b->h_counts.h + d.co;
-  out->ordered = b->h_scal[(size_t)g * 8 + 4];
-  out->calls = d.K;
-  return HGE_OK;
-}
-
-int hge_gossip_params_check(int32_t n_participants, const hge_gossip_params* p, int32_t n_graphs) {
-  if (!p || n_participants < 1 || n_participants > 64 || n_graphs < 1) return HGE_ERR_ARG;
-  if (p->events < n_participants || p->events > HGE_GOSSIP_MAX_EVENTS || p->forkers < 0 || p->k < 1) return HGE_ERR_ARG;
-  if (!(p->fork_p >= 0.0 && p->fork_p <= 1.0) || !(p->cascade_p >= 0.0 && p->cascade_p <= 1.0)) return HGE_ERR_ARG;
-  if (p->op_lag < 0 || p->op_lag > HGE_GOSSIP_MAX_OP_LAG) return HGE_ERR_ARG;
-  return HGE_OK;
-}
-
-int hge_batch_generate(hge_batch* b, const hge_gossip_params* p, int32_t n_graphs, uint64_t seed0) {
-  if (!b) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  static_assert(HGE_GOSSIP_MAX_OP_LAG < GLAG && 5ll * HGE_GOSSIP_MAX_EVENTS < (1 << 24), "kg_walk's ring and map entry");
-  if (hge_gossip_params_check(b->N, p, n_graphs) != HGE_OK)
-    throw Error{HGE_ERR_ARG, "hge_batch_generate: bad argument (hge_gossip_params_check)"};
-  b->generate(*p, n_graphs, seed0);
-  return HGE_OK;
-  BGUARD_END(b)
-}
-
-int hge_stats_spec_check(const hge_stats_spec* s) { return hge_stats::spec_ok(s) ? HGE_OK : HGE_ERR_ARG; }
-
-int64_t hge_stats_hist_len(const hge_stats_spec* s) {
-  return hge_stats::spec_ok(s) ? hge_stats::hist_len(*s) : (int64_t)HGE_ERR_ARG;
-}
-
-int hge_batch_stats(hge_batch* b, const hge_stats_spec* s, int64_t* graph_rows, int64_t* hist, int64_t* graph_hist) {
-  if (!b) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  if (!hge_stats::spec_ok(s)) throw Error{HGE_ERR_ARG, "hge_batch_stats: bad spec (hge_stats_spec_check)"};
-  if (!hist) throw Error{HGE_ERR_ARG, "hge_batch_stats: hist is NULL"};
-  if (!b->stats_ok)
-    throw Error{HGE_ERR_ARG, "hge_batch_stats: no run since the batch last changed (hge_batch_run)"};
-  b->stats(*s, graph_rows, hist, graph_hist);
-  return HGE_OK;
-  BGUARD_END(b)
-}
-
-int hge_batch_clear(hge_batch* b) {
-  if (!b) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  if (b->st) HGE_HIPCHK(hipStreamSynchronize(b->st));
-  b->clear();
-  return HGE_OK;
-  BGUARD_END(b)
-}
-
-int64_t hge_batch_submissions(hge_batch* b, int32_t g, hge_event* ev_out, int32_t* status_out, int64_t cap) {
-  if (!b || g < 0 || g >= b->graphs()) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  return b->submissions(g, ev_out, status_out, cap);
-  BGUARD_END(b)
-}
-
-int hge_batch_launch_plan(hge_batch* b, int32_t* out, int32_t cap) {
-  if (!b || (!out && cap > 0)) return HGE_ERR_ARG;
-  const hge_batch::Plan& p = b->plan;
-  const int32_t f[] = {b->ncu, p.nm, p.coords, p.front_threads, p.ns, p.sort_threads, p.consensus_occ, p.dlv};
-  const int n = (int)(sizeof(f) / sizeof(f[0]));
-  for (int k = 0; k < n && k < cap; k++) out[k] = f[k];
-  return n;
-}
-
-int hge_batch_kernel_ms(hge_batch* b, float* ms, int32_t cap) {
-  if (!b || (!ms && cap > 0)) return HGE_ERR_ARG;
-  for (int k = 0; k < hge_batch::NK && k < cap; k++) ms[k] = b->kms[k];
-  return hge_batch::NK;
-}
-
-}  // extern "C"
-
-// diagnostics (not part of the C ABI): graph g's lastAncestors (which 0) or
-// firstDescendants (which 1) rows after a run, E x N int32 into out
-extern "C" int hgb_debug_rows(hge_batch* b, int32_t g, int32_t which, int32_t* out) {
-  if (!b || !out || g < 0 || g >= b->graphs() || !b->ran) return HGE_ERR_ARG;
-  BGUARD_BEGIN
-  const GDesc& d = b->hd[g];
-  if (which == 2)  // the run layout FDT[j][c][p], N x N x ccap
-    b->down(out, b->d_FDT.p + (size_t)g * b->N * b->N * b->ccap, (size_t)b->N * b->N * b->ccap);
-  else
-    b->down(out, b->d_LA.p + d.eo * b->N, (size_t)d.E * b->N);
-  return HGE_OK;
-  BGUARD_END(b)
-}
+// host side: struct hge_batch and the C ABI
+#include "hge_batch_host.hip"

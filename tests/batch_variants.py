@@ -1,7 +1,7 @@
 """Batches past the batch engine's size thresholds, at the widths where its kernels
 change path (a test helper; tests/test_batch_variants.py, tests/test_gpu_batch_variants.py).
 
-hge_batch::run_stages and run choose a template instance of almost every batch kernel
+A run launches a template instance of almost every batch kernel chosen (hge_batch_plan.h)
 from the batch's size against the device's compute-unit count (DESIGN.md §4.8;
 Batch.launch_plan() names the choice), and inside kb_front the thread count selects one
 (member, chain) pair per thread while N * N fits the workgroup, a strided loop above:

@@ -1,8 +1,8 @@
 """The batch kernels chosen by the batch's size, at every width where a path flips,
 against the oracle: exactly, field by field, for every graph of the batch.
 
-hge_batch::run_stages and run pick the instance of kb_coords, kb_front, kb_pairs /
-kb_fold, kb_sort's first class and kb_consensus from the number of graphs G, of calls and
+A run launches the instance of kb_coords, kb_front, kb_pairs / kb_fold, kb_sort's first
+class and kb_consensus that hge_batch_plan.h picks from the number of graphs G, of calls and
 of fallback graphs against the device's compute-unit count.  The rest of
 the suite runs at G <= about 50 and so under the first row of every rule, but for two
 batches of config 5's shape (N = 32).  Here G_mid = cus + 8 and G_big = 2 * cus + 8
