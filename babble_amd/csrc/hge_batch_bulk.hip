@@ -848,7 +848,8 @@ __global__ __launch_bounds__(TPB) void kb_sort(BT t, int last) {
           cmx = max(cmx, s_red64[k][1]);
         }
       }
-      const bool fits = rmx - rmn < 16 && cmx - cmn < ((int64_t)1 << 28);
+      // (the span unsigned: two timestamps 2^63 ns or more apart wrap a signed difference)
+      const bool fits = rmx - rmn < 16 && (uint64_t)cmx - (uint64_t)cmn < (1ull << 28);
       for (int k = tid; k < n; k += TPB) {
         lk[k] = fits ? ((uint64_t)(t.krr[so + k] - rmn) << 60) | ((uint64_t)(t.kct[so + k] - cmn) << 32) |
                            (t.ks0[so + k] >> 32)

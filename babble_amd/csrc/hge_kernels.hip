@@ -2803,8 +2803,8 @@ __device__ void bucket_sort_one(int b, const int32_t* bend, const int32_t* bcnt,
     for (int i = tid; i < n; i += T) ids_out[start + i] = (int32_t)sc.id[sc.ix[i]];
     return;
   }
-  // large bucket (past 2 * BIG_SORT, or every one with HGE_BIG_SORT=0): sorted
-  // CH-key chunks, then pairwise merges (ping-pong)
+  // large bucket (past 2 * BIG_SORT; k_bucket_sort_big takes those of CH + 1 .. 2 * BIG_SORT
+  // keys): sorted CH-key chunks, then pairwise merges (ping-pong)
   OKey* src = keys + start;
   OKey* dst = tmp + start;
   for (int c0 = 0; c0 < n; c0 += CH) {

@@ -21,7 +21,9 @@ exact rank search, kb_consensus's twin of it, the register sort's filler value),
 buckets whose timestamps span 2^28 ns or more (kb_sort unpacked, every comparison from
 HBM) or one less (the packed field's top bit), and keys equal down to S's last limb
 (key_less past the first limb in every sort).  One branch no stream reaches: a call
-bucket received over 16 rounds or more, the other half of kb_sort's packing condition."""
+bucket received over 16 rounds or more, the other half of kb_sort's packing condition.
+test_gpu_sort_kernels.py drives kb_sort alone on such buckets (a round span of exactly 15,
+16 and 40; tests/abi/hge_batch_sort_kernel_test.hip)."""
 import os
 import sys
 
